@@ -16,25 +16,30 @@ Inputs (images, gallery slab) are resident in HBM before the timed region.  Weak
 rank extracts B images and holds a 10k-row gallery shard.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full --dump-outputs bench_outputs/   # + everything below; the last step's lists as .npy
     python bench.py --gpus 8                      # self-launching: starts its eight ranks itself (no launcher process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 3
 
-Rank 0 prints the record twice: first `{"bench_detail": {...}}` -- everything (per-family and per-layer-shape rooflines, every
-side measurement in full), also written to `bench_detail.json` (gpurun_out/ when that directory exists, else next to this
-file) -- and then, as the LAST stdout line, the compact record the driver parses (<= 6 KB: metric / value / ms_per_step / config /
-ONE `roofline` for the dominant kernel family / `roofline_step` / `retrieval_shard` / `extraction_regions` / `cpu_baseline`).
+A plain run sets up, warms up, times the K steps and prints ONE line on rank 0: the headline (metric / value / ms_per_step / config /
+`roofline_step`, which is priced from ms_per_step alone).  `--dump-outputs DIR` writes the ranked lists of the last timed step
+(topk_scores.npy float32, topk_indices.npy float64; inputs are seeded, so two builds can be compared output for output).
+
+`--full` adds everything else, outside the timed region.  Rank 0 then prints the record twice: first `{"bench_detail": {...}}` --
+everything (per-family and per-layer-shape rooflines, every side measurement in full), also written to `bench_detail.json`
+(bench_legs/line.py:write_detail) -- and then, as the LAST stdout line, the compact record the driver parses (<= 6 KB: metric / value /
+ms_per_step / config / ONE `roofline` for the dominant kernel family / `roofline_step` / `retrieval_shard` / `extraction_regions` / `cpu_baseline`).
 The K timed steps carry no per-kernel instrumentation; the per-kernel HIP-event timings behind the `roofline*` objects come
 from a separate instrumented pass over the same step.
 
 N > 1: the search stage of step i (all-gather of the query descriptors, score GEMM against this rank's shard, top-k, all-gather of the
 per-shard lists + isx_topk_merge) is issued on a second HIP stream behind an event and rides behind the trunk of step i + 1
-(`--no-overlap-exchange` keeps everything on one stream); `exchange_ms` is what the query all-gather, the two result all-gathers
+(`--no-overlap-exchange` keeps everything on one stream); with `--full`, `exchange_ms` is what the query all-gather, the two result all-gathers
 and the merge cost when nothing hides them (HIP events in the instrumented pass), `overlap_identical` says that both
 schedules returned the same bits.  `cpu_baseline` is timed on
 rank 0 at every N (the other ranks wait at the barrier).
 
-Side objects of the same line (each bounded to a few seconds; a failure in one is reported inside it and never costs the
+Side objects of the `--full` line (each bounded to a few seconds; a failure in one is reported inside it and never costs the
 headline): `retrieval_shard` = BASELINE configs[4]'s per-GPU shard (10k x 125k x 2048) end to end; `extraction_regions` =
 BASELINE configs[2]: ResNet-50 TuneClassifSub on 448 x 448 images -> best-location class-score descriptors (reference
 train/classif_regions.py:107-132) with its own roofline, plus the 1k x 100k retrieval + metrics leg of that config.
@@ -88,7 +93,33 @@ def parse():
                     help="images of the non-resident streaming-ingest side measurement (0 = skip); host memory: 4096 distinct uint8 images, the rest views")
     ap.add_argument("--no-train-bench", action="store_true", help="skip the siamese-training side measurement (BASELINE configs[3] on one GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline: the N > 1 schedule and merge checks, the instrumented "
+                         "per-kernel pass, the side legs, cpu_baseline, and print the full record (the --no-* options above select within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the ranked lists of the last timed step to DIR/topk_scores.npy (float32) and DIR/topk_indices.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6     # array bytes of one dump: under 64 MB with the .npy headers
+
+
+def dump_outputs(path, scores, indices):
+    """The (M, k) lists the timed path returned in its last step.  Above DUMP_MAX_BYTES in all, a fixed seeded sample of rows is written,
+    with the row numbers in topk_rows.npy."""
+    import numpy as np
+    s, i = scores.float().cpu().numpy(), indices.cpu().numpy().astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    per_row = s.shape[1] * (4 + 8) + 8
+    if s.shape[0] * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(s.shape[0], DUMP_MAX_BYTES // per_row, replace=False))
+        s, i = s[rows], i[rows]
+        np.save(os.path.join(path, "topk_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "topk_scores.npy"), s)
+    np.save(os.path.join(path, "topk_indices.npy"), i)
 
 
 def self_launch(args):
@@ -192,6 +223,13 @@ def main():
         except Exception as e:
             return {"error": "%s: %s" % (type(e).__name__, e)}
 
+    def close():
+        if world > 1:
+            dist.barrier()
+            torch.cuda.synchronize()
+            retrieval.close_native_comms()
+            dist.destroy_process_group()
+
     if args.only_regions:                            # profiling aid: `rocprofv3 --kernel-trace -- python3 bench.py --only-regions` traces this leg alone
         out_r = leg_regions.measure(ctx)
         if rank == 0:
@@ -291,6 +329,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     assert out[1].shape == (M, k) and int(out[1].min()) >= 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[0], out[1])
+    gemm_flop = 2.0 * M * Ng * D
+    ctx.dt, ctx.gemm_flop = dt, gemm_flop
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(compact_line(report.headline(ctx))), flush=True)
+        close()
+        return
     overlap_identical = None
     merge_identical = None
     if world > 1:
@@ -349,11 +396,9 @@ def main():
             t["floor_ms"] += max(flop / (PEAK_F32_MFMA_TFLOPS * 1e9), nbytes / (PEAK_HBM_GBS * 1e6))
         if world > 1:
             dist.barrier()
-    gemm_flop = 2.0 * M * Ng * D
     gap_bytes = B * D * 49 * 4 + B * D * 4
 
     # ---- side legs (outside the timed region; bench_legs/) ---------------------------------------------------------------------------------
-    ctx.dt = dt
     shard_result = None
     if not args.no_shard_bench:                      # BASELINE configs[4]'s per-GPU shard: 10 k queries x 125 k rows, exact-fast and all-fp32, sharded AP
         shard_result = side_leg(leg_shard.measure, on_every_rank=True)
@@ -407,11 +452,7 @@ def main():
         detail_file = write_detail(line)
         print(json.dumps({"bench_detail": line}), flush=True)          # everything, on an EARLIER line (and in the side file)
         print(json.dumps(compact_line(line, detail_file)), flush=True)      # the driver's line: last on stdout, <= 6 KB
-    if world > 1:
-        dist.barrier()
-        torch.cuda.synchronize()
-        retrieval.close_native_comms()
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

@@ -7,7 +7,6 @@ def assemble(ctx):
     """Rank 0: the measurements of the run -> the full record (contract fields, one roofline object per kernel family with its per-layer-shape table,
     `roofline` = the dominant family + north_star's named kernels, the side legs).  cpu_baseline is added by the caller."""
     B, D, M, Ng, args, backend, cl, dt, exchange_legs, gap_bytes, gap_ms, gemm_flop, gemm_ms, ingest_decode_result, ingest_result, k, ksteps, merge_identical, overlap, overlap_identical, regions_result, retrieval, shard_result, slab_result, training_result, trunk, world = ctx.B, ctx.D, ctx.M, ctx.Ng, ctx.args, ctx.backend, ctx.cl, ctx.dt, ctx.exchange_legs, ctx.gap_bytes, ctx.gap_ms, ctx.gemm_flop, ctx.gemm_ms, ctx.ingest_decode_result, ctx.ingest_result, ctx.k, ctx.ksteps, ctx.merge_identical, ctx.overlap, ctx.overlap_identical, ctx.regions_result, ctx.retrieval, ctx.shard_result, ctx.slab_result, ctx.training_result, ctx.trunk, ctx.world
-    images_per_s = world * B * args.steps / dt
     ms_per_step = 1000.0 * dt / args.steps
     traffic = load_traffic()
     tsrc = traffic.get("source")
@@ -26,26 +25,7 @@ def assemble(ctx):
             return None                    # the profile was taken with a different kernel dispatch: stale, not reported
         return e.get("bytes")
 
-    line = {
-        "metric": "images/sec descriptor extract + query x gallery search",
-        "value": images_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: ResNet-50 fully-conv global descriptors + top-%d cosine search, "
-                               "%d-row gallery shard per GPU, 224x224 synthetic images" % (k, Ng),
-                   "images_per_gpu_per_step": B, "gallery_rows_per_gpu": Ng, "descriptor_dim": D, "k": k,
-                   "backbone": args.backbone, "backbone_dtype": args.backbone_dtype, "activation_layout": "NHWC" if cl else "NCHW",
-                   "bn_folded": not args.no_fold_bn, "parallelism": "gallery-row shards x%d + DP extraction" % world,
-                   "collective_backend": backend, "ranks": world},
-        "dist_per_s": images_per_s * Ng * world,
-    }
-    # whole step against the fp32 matrix-core peak (ResNet-50 convolutions + the distance GEMM; pooling / top-k are bytes, not FLOP)
-    step_flop = RESNET50_GFLOP_PER_IMAGE * 1e9 * B + gemm_flop if args.backbone == "resnet50" else None
-    if step_flop:
-        line["roofline_step"] = {"bound": "mfma", "achieved": step_flop / (ms_per_step * 1e-3) / 1e12, "peak": PEAK_F32_MFMA_TFLOPS,
-                                 "unit": "TFLOP/s", "frac": step_flop / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                                 "algorithmic_flop_per_step_per_gpu": step_flop,
-                                 "note": "%.2f GFLOP per image (ResNet-50 convolutions) x %d images + 2*M*N*D of the search" % (RESNET50_GFLOP_PER_IMAGE, B)}
+    line = headline(ctx)
     fam = {}
     kernel_names = {
         "isx_conv1x1_nhwc": "conv1x1_tail_kernel / cosine_gemm_kernel<ALIGNED, TM, TN, EPI = 2, BK> + conv1x1_stream_kernel for Cin = 64 (isx_conv1x1_nhwc: 1x1 convolutions as fp32-MFMA GEMMs over the pixels, bias/residual/ReLU fused)",
@@ -147,4 +127,32 @@ def assemble(ctx):
                                 legs="query all-gather | per-shard top-k all-gather x 2 + isx_topk_merge"
                                      + (" (with the score GEMM and the top-k between them on a second stream, behind the next step's trunk)" if overlap else ""),
                                 timing="HIP events on the launch stream, max over ranks, %d instrumented steps with the exchange in line" % ksteps)
+    return line
+
+
+def headline(ctx):
+    """The contract fields of the record, from the timed region alone (ctx.dt, ctx.gemm_flop): what a plain run prints, the head of the full record."""
+    B, D, Ng, args, backend, cl, dt, gemm_flop, k, world = ctx.B, ctx.D, ctx.Ng, ctx.args, ctx.backend, ctx.cl, ctx.dt, ctx.gemm_flop, ctx.k, ctx.world
+    images_per_s = world * B * args.steps / dt
+    ms_per_step = 1000.0 * dt / args.steps
+    line = {
+        "metric": "images/sec descriptor extract + query x gallery search",
+        "value": images_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: ResNet-50 fully-conv global descriptors + top-%d cosine search, "
+                               "%d-row gallery shard per GPU, 224x224 synthetic images" % (k, Ng),
+                   "images_per_gpu_per_step": B, "gallery_rows_per_gpu": Ng, "descriptor_dim": D, "k": k,
+                   "backbone": args.backbone, "backbone_dtype": args.backbone_dtype, "activation_layout": "NHWC" if cl else "NCHW",
+                   "bn_folded": not args.no_fold_bn, "parallelism": "gallery-row shards x%d + DP extraction" % world,
+                   "collective_backend": backend, "ranks": world},
+        "dist_per_s": images_per_s * Ng * world,
+    }
+    # whole step against the fp32 matrix-core peak (ResNet-50 convolutions + the distance GEMM; pooling / top-k are bytes, not FLOP)
+    step_flop = RESNET50_GFLOP_PER_IMAGE * 1e9 * B + gemm_flop if args.backbone == "resnet50" else None
+    if step_flop:
+        line["roofline_step"] = {"bound": "mfma", "achieved": step_flop / (ms_per_step * 1e-3) / 1e12, "peak": PEAK_F32_MFMA_TFLOPS,
+                                 "unit": "TFLOP/s", "frac": step_flop / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                                 "algorithmic_flop_per_step_per_gpu": step_flop,
+                                 "note": "%.2f GFLOP per image (ResNet-50 convolutions) x %d images + 2*M*N*D of the search" % (RESNET50_GFLOP_PER_IMAGE, B)}
     return line

@@ -121,3 +121,47 @@ def test_cpu_baseline_retrieval_runs_on_the_host():
     out = b.cpu_baseline_retrieval(argparse.Namespace(k=100), seconds=0.2)
     assert out["unit"] == "distances/s" and out["value"] > 1e6 and out["cores"] >= 1 and out["kind"] == "port"
     assert out["ap_loop_ms_per_query"] > 0 and "ap_loop_error" not in out
+
+
+def test_plain_run_prints_the_head_of_the_full_record(monkeypatch):
+    """A plain run (no --full) prints compact_line(report.headline(ctx)): the contract's fields, worded as in the committed full records, with
+    value and ms_per_step from the timed region alone; --steps sets the timed steps and must be at least 1."""
+    import sys
+    import types
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = b.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7
+    ctx = types.SimpleNamespace(args=args, B=args.batch, D=2048, Ng=args.gallery, k=args.k, world=1, backend=None, cl=True, dt=0.5,
+                                gemm_flop=2.0 * args.batch * args.gallery * 2048)
+    line = json.loads(json.dumps(b.compact_line(b.report.headline(ctx))))
+    assert line["ms_per_step"] == pytest.approx(1000.0 * 0.5 / 7) and line["value"] == pytest.approx(args.batch * 7 / 0.5)
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["roofline"] is None and "detail_file" not in line
+    full = _full_records()[-1][1]
+    for key in ("metric", "unit", "higher_is_better", "dtype", "scaling", "data"):
+        assert line[key] == full[key], key
+    assert set(line["config"]) == set(full["config"]) and set(line["roofline_step"]) <= set(full["roofline_step"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
+def test_dump_outputs_float_arrays_under_the_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's (M, k) lists as float32 scores and float64 indices; above the cap, the same seeded sample of rows every time."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    s, i = torch.rand(50, 10, generator=g), torch.randint(0, 1 << 30, (50, 10), generator=g, dtype=torch.int64)
+    b.dump_outputs(str(tmp_path / "a"), s, i)
+    got_s, got_i = np.load(tmp_path / "a" / "topk_scores.npy"), np.load(tmp_path / "a" / "topk_indices.npy")
+    assert got_s.dtype == np.float32 and got_i.dtype == np.float64 and not (tmp_path / "a" / "topk_rows.npy").exists()
+    assert np.array_equal(got_s, s.numpy()) and np.array_equal(got_i.astype(np.int64), i.numpy())
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 20 * (10 * 12 + 8))
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), s, i)
+    rows = np.load(tmp_path / "b" / "topk_rows.npy").astype(np.int64)
+    assert len(rows) == 20 and np.array_equal(rows, np.load(tmp_path / "c" / "topk_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "topk_scores.npy"), s.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "topk_indices.npy"), np.load(tmp_path / "c" / "topk_indices.npy"))
+    assert sum(np.load(tmp_path / "b" / n).nbytes for n in ("topk_rows.npy", "topk_scores.npy", "topk_indices.npy")) <= b.DUMP_MAX_BYTES

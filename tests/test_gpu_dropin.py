@@ -387,7 +387,7 @@ def test_bench_multi_rank_code_path_on_one_gpu():
     env = dict(os.environ, ISX_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--full",
            "--gallery", "2000", "--cpu-seconds", "2", "--no-shard-bench", "--no-regions-bench", "--ingest-images", "0"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -431,7 +431,7 @@ def test_bench_three_ranks_on_one_gpu():
     env = dict(os.environ, ISX_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--batch", "24",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--batch", "24", "--full",
            "--gallery", "1500", "--no-cpu-baseline", "--no-shard-bench", "--no-regions-bench", "--ingest-images", "0"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -439,6 +439,36 @@ def test_bench_three_ranks_on_one_gpu():
     assert d["n_gpus"] == 3 and d["config"]["ranks"] == 3 and d["config"]["gallery_rows_per_gpu"] == 1500 and d["value"] > 0
     ex = d["exchange"]
     assert ex["overlap_identical"] is True and ex["merged_lists_identical_to_unsharded_search"] is True and ex["communicators_in_data_path"] == 1
+
+
+def test_bench_plain_run_dumps_the_same_lists_twice(tmp_path):
+    """`python bench.py` without --full: ONE JSON line, the headline only (no side legs, no per-kernel pass), and --dump-outputs writes the ranked
+    lists of the last timed step -- the same bits on a second run (seeded inputs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ISX_BENCH_ONE_DEVICE"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32", "--gallery", "2000",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and out.stdout.rstrip().splitlines()[-1] == lines[0]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "images/s" and d["dtype"] == "f32"
+        assert d["value"] == pytest.approx(32 * 1000.0 / d["ms_per_step"], rel=1e-9) and d["roofline"] is None
+        assert not any(key in d for key in ("cpu_baseline", "retrieval_shard", "extraction_regions", "training", "families", "detail_file"))
+        dumps.append([np.load(tmp_path / run / n) for n in ("topk_scores.npy", "topk_indices.npy")])
+    (s, i), (s2, i2) = dumps
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (32, 100)
+    assert np.all(np.diff(s, axis=1) <= 0) and i.min() >= 0 and i.max() < 2000 and np.all(i == np.round(i))
+    assert np.array_equal(s, s2) and np.array_equal(i, i2)
 
 
 def test_descriptor_head_golden_on_gpu(golden):

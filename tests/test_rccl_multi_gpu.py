@@ -77,7 +77,7 @@ def test_rccl_sharded_search_and_grad_allreduce(tmp_path):
 def test_bench_all_gpus_bare_command_line():
     """`python bench.py --gpus N` (N = every GPU of the box, at most 8) with nothing around it: self-launch, RCCL, one JSON line."""
     n = min(_n_gpus(), 8)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "64", "--full",
            "--gallery", "4000", "--no-shard-bench"]
     p = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
