@@ -14,13 +14,8 @@
  *   - every call only ENQUEUES work on `stream` (a hipStream_t passed as void*) and
  *     returns; no allocation, no synchronisation, no global state in the entry points
  *     declared here: safe to capture in a hipGraph and re-entrant from several host
- *     threads on distinct streams.  (The library also exports four UNDECLARED
- *     process-global A/B hooks -- isx_debug_set_gemm_cfg, isx_debug_set_conv_cfg,
- *     isx_debug_set_f16_tile, isx_debug_fast_fallback_rows -- for tests and
- *     scratch/ timing scripts: they force a tile shape for every later call of
- *     the process (relaxed atomics: flipping one while another host thread
- *     launches is a data-race-free way to get either tile shape), never change a
- *     result, and are not part of this ABI.)
+ *     threads on distinct streams (the test hooks at the end of this file are the
+ *     exception)
  *   - environment, read once per process, tuning only (no value changes a result):
  *     ISX_TAIL_SPLIT=0 (128x128 grids without the 64x64 tail), ISX_TOPK_CHUNK_MB
  *     (score-chunk budget of the running top-k, default 1024), ISX_TOPK_FIRST
@@ -466,6 +461,26 @@ int isx_colsum_leaves(const float* x, int leaves, int R, int64_t C, float* out, 
  * added, chosen so that 1, 2, 4, 8 ranks produce the same bits).  rows: L rows of n floats, `stride` floats apart; out may be rows' row 0.
  * 1 <= L <= 16.  One pass over the L rows instead of L - 1 add passes. */
 int isx_tree_sum_rows(const float* rows, int L, int64_t stride, int64_t n, float* out, isx_stream_t stream);
+
+/* ---- test hooks -------------------------------------------------------------
+ * For the test suite and the timing tools, not for production callers.  They are PROCESS-GLOBAL:
+ * a setter forces a tile shape for every later call of the process, on every device and
+ * stream (relaxed atomics: flipping one while another host thread launches gives either
+ * tile shape, without a data race).  No hook changes a result: every tile shape computes
+ * the same bits. */
+
+/* Score / 1x1-convolution GEMM tile: 0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64, -1 = automatic.
+ * Initial value from the environment variable ISX_DEBUG_GEMM_CFG. */
+void isx_debug_set_gemm_cfg(int c);
+/* Trunk convolution tiles: 0 = 128x128, 2 = 128x64, 3 = 64x64 (3x3 and dual 1x1 kernels); 7 = automatic
+ * without the 64x64 tails; 9 = the general 1x1 path instead of the streaming kernel; -1 = automatic.
+ * Initial value from the environment variable ISX_DEBUG_CONV_CFG. */
+void isx_debug_set_conv_cfg(int c);
+/* fp16 filter GEMM of isx_cosine_topk_fast: 0 = 128x128, 1 = 256x256, 2 = 256x256 register-staged, -1 = automatic. */
+void isx_debug_set_f16_tile(int t);
+/* Query rows of the LAST isx_cosine_topk_fast call on workspace `ws` (same arguments) that took the exact
+ * fp32 fallback; -1 when that call ran the fp32 search as a whole.  Synchronises the device. */
+int isx_debug_fast_fallback_rows(const void* ws, int64_t M, int64_t N, int D, int k, int have_gallery_f16);
 
 #ifdef __cplusplus
 }

@@ -31,8 +31,7 @@ int launch_gemm_masked(const float* A, int64_t M, const float* Bt, int64_t N, in
 // third of each launch ran half empty (wgrad 3.3 ms per step for 311 GFLOP = 0.60 of the fp32 peak).
 static int wgrad_splits(int64_t K, int Cin, int Cout, int taps) {
     const int64_t nk = (K + 31) / 32;
-    static const int64_t target = [] { const char* e = getenv("ISX_WGRAD_TARGET"); const long long v = e ? atoll(e) : 0; return (int64_t)(v >= 64 ? v : 0); }();   // A/B knob: > 0 = the rule of rounds 4-5a (blocks per leaf)
-    if (target == 0 && Cout % 128 == 0 && Cin % 128 == 0 && nk >= 8) {
+    if (Cout % 128 == 0 && Cin % 128 == 0 && nk >= 8) {
         const int64_t n128 = (int64_t)(Cout / 128) * (Cin / 128) * taps;
         int best = 1;
         double best_t = 1e300;
@@ -43,10 +42,10 @@ static int wgrad_splits(int64_t K, int Cin, int Cout, int taps) {
         }
         return best;
     }
+    // other shapes: about 512 blocks per leaf
     const bool big = Cout % 128 == 0 && Cin % 128 == 0 && (int64_t)(Cout / 128) * (Cin / 128) * taps >= 512;
     const int64_t tiles = (big ? (int64_t)(Cout / 128) * (Cin / 128) : (int64_t)(Cout / 64) * (Cin / 64)) * taps;
-    const int64_t tgt = target > 0 ? target : 512;
-    int64_t s = (tgt + tiles - 1) / tiles;
+    int64_t s = (512 + tiles - 1) / tiles;
     if (s > nk / 4) s = nk / 4;
     if (s > 16) s = 16;
     return (int)(s < 1 ? 1 : s);

@@ -24,7 +24,7 @@ __device__ __forceinline__ void conv3x3_tile(float* __restrict__ lds, const floa
                                              const Conv3x3Geom& g, float* __restrict__ C, int64_t m0, int64_t n0,
                                              const float* __restrict__ bias, const float* __restrict__ res, int relu, const float* __restrict__ mask = nullptr) {
     f32x16 acc[TM][TN];
-    conv3x3_mainloop<TM, TN, BK, false, 2, CHUNK>(lds, x, M, Wt, N, g, m0, n0, acc);
+    conv3x3_mainloop<TM, TN, BK, false, CHUNK>(lds, x, M, Wt, N, g, m0, n0, acc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm_u = __builtin_amdgcn_readfirstlane(wave >> 1), wn_u = __builtin_amdgcn_readfirstlane(wave & 1);
     // residual / mask look-ahead by register budget: gradient kernels (CHUNK == 0, 116 of 128 VGPRs) one tile at a time, 128x128 inference tiles two
@@ -33,7 +33,7 @@ __device__ __forceinline__ void conv3x3_tile(float* __restrict__ lds, const floa
 
 // workgroups per CU: 64x64 tiles 6; 128x64 4 (two-level: 126 VGPRs); 128x128 4 with one accumulator set (gradients), 2 with two (64 + 64 accumulator VGPRs)
 template <int TM, int TN, int BK, bool GRAD>
-__global__ __launch_bounds__(256, TM * TN == 1 ? 6 : (TM * TN == 4 && !GRAD) ? ISX_WG_PER_CU_128 : 4) void conv3x3_nhwc_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N,
+__global__ __launch_bounds__(256, TM * TN == 1 ? 6 : (TM * TN == 4 && !GRAD) ? kWgPerCu128 : 4) void conv3x3_nhwc_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N,
                                                            Conv3x3Geom g, float* __restrict__ C, TileMap tm,
                                                            const float* __restrict__ bias, const float* __restrict__ res, int relu, const float* __restrict__ mask) {
     __shared__ float lds[BK * (64 * TM + 64 * TN + 2 * lds_pad(BK))];
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256, TM * TN == 1 ? 6 : (TM * TN == 4 && !GRAD) ? I
 // with a few 128x128 tiles running alone on their CUs at half the matrix-pipe rate while the other CUs idle -- 256->256 at 14x14, B = 1024:
 // 3136 tiles = 3 rounds + 64 tiles, 256 us of tail in a 1.79 ms launch.  Here the rows past the last whole round are cut into 64x64
 // tiles (a quarter of the work each, four times as many): the same blocks of the grid, same arithmetic per output element.
-__global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv3x3_tail_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N, Conv3x3Geom g,
+__global__ __launch_bounds__(256, kWgPerCu128) void conv3x3_tail_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N, Conv3x3Geom g,
                                                               float* __restrict__ C, TileMap tm_big, TileMap tm_small, int64_t m_split,
                                                               const float* __restrict__ bias, const float* __restrict__ res, int relu) {
     constexpr int kBig = 16 * (128 + 128 + 2 * lds_pad(16));
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv3x3_tail_kernel(co
         conv3x3_tile<2, 2, 16>(lds, x, M, Wt, N, g, C, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, res, relu);
     } else {
         tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        conv3x3_tile<ISX_TAIL_TM, 1, 32>(lds, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * (64 * ISX_TAIL_TM), (int64_t)tile_n * 64, bias, res, relu);
+        conv3x3_tile<1, 1, 32>(lds, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, res, relu);
     }
 }
 
@@ -69,12 +69,12 @@ static void launch_conv3x3(const float* x, int64_t M, const float* w, int64_t N,
     tm.m_active = nullptr;
     tm.tiles_m = (int)((M + 64 * TM - 1) / (64 * TM));
     tm.tiles_n = (int)((N + 64 * TN - 1) / (64 * TN));
-    const int64_t split = (TM == 2 && TN == 2 && !mask) ? gemm_tail_split_rows(M, N, 256 * ISX_WG_PER_CU_128) : 0;
+    const int64_t split = (TM == 2 && TN == 2 && !mask) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
     if (split > 0) {
         TileMap small;
         small.m_active = nullptr;
         tm.tiles_m = (int)(split / 128);
-        small.tiles_m = (int)((M - split + 64 * ISX_TAIL_TM - 1) / (64 * ISX_TAIL_TM));
+        small.tiles_m = (int)((M - split + 63) / 64);
         small.tiles_n = (int)((N + 63) / 64);
         hipLaunchKernelGGL(conv3x3_tail_kernel, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y,
                            tm, small, split, bias, res, relu);
@@ -163,7 +163,7 @@ __device__ __forceinline__ void conv1x1_dual_tile(float* __restrict__ lds, const
 
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = kConvChunk != 0 && TM * TN == 4 && ISX_PIN_KTILE;
+    constexpr bool PINNED = kConvChunk != 0 && TM * TN == 4;
     KtilePtrs<BK> pins;
     if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
     // outer loop: chunks of the two-level sum over the flattened [t ; x] reduction; inner loop: the staged k-tiles of a chunk (gemm_tile.hpp); the
@@ -189,11 +189,11 @@ __device__ __forceinline__ void conv1x1_dual_tile(float* __restrict__ lds, const
     } else {
         for (int kt = 0; kt < nk;) {
             const int kend = kt + kConvChunk / BK < nk ? kt + kConvChunk / BK : nk;
-            body(kt++, std::true_type());                      // (interleaved fold: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
+            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
             for (; kt < kend; ++kt) body(kt, std::false_type());
-            if (!((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2)) add_chunk<TM, TN>(tot, acc);
+            if (!PINNED) add_chunk<TM, TN>(tot, acc);
         }
-        if ((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2) add_chunk<TM, TN>(tot, acc);       // the last chunk
+        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
     }
     if constexpr (kConvChunk != 0) {
 #pragma unroll
@@ -207,7 +207,7 @@ __device__ __forceinline__ void conv1x1_dual_tile(float* __restrict__ lds, const
 }
 
 template <int TM, int TN, int BK>
-__global__ __launch_bounds__(256, TM * TN == 1 ? 6 : TM * TN == 4 ? ISX_WG_PER_CU_128 : 4) void conv1x1_dual_nhwc_kernel(const float* __restrict__ t, const float* __restrict__ x, int64_t M,
+__global__ __launch_bounds__(256, TM * TN == 1 ? 6 : TM * TN == 4 ? kWgPerCu128 : 4) void conv1x1_dual_nhwc_kernel(const float* __restrict__ t, const float* __restrict__ x, int64_t M,
                                                                                       const float* __restrict__ Wt, int64_t N, DualGeom g,
                                                                                       float* __restrict__ C, TileMap tm,
                                                                                       const float* __restrict__ bias, int relu) {
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256, TM * TN == 1 ? 6 : TM * TN == 4 ? ISX_WG_PER_C
 }
 
 // 128x128 tiles + 64x64 tail in one grid (see conv3x3_tail_kernel)
-__global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv1x1_dual_tail_kernel(const float* __restrict__ t, const float* __restrict__ x, int64_t M, const float* __restrict__ Wt,
+__global__ __launch_bounds__(256, kWgPerCu128) void conv1x1_dual_tail_kernel(const float* __restrict__ t, const float* __restrict__ x, int64_t M, const float* __restrict__ Wt,
                                                                    int64_t N, DualGeom g, float* __restrict__ C, TileMap tm_big, TileMap tm_small,
                                                                    int64_t m_split, const float* __restrict__ bias, int relu) {
     constexpr int kBig = 16 * (128 + 128 + 2 * lds_pad(16));
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv1x1_dual_tail_kern
         conv1x1_dual_tile<2, 2, 16>(lds, t, x, M, Wt, N, g, C, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, relu);
     } else {
         tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        conv1x1_dual_tile<ISX_TAIL_TM, 1, 32>(lds, t, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * (64 * ISX_TAIL_TM), (int64_t)tile_n * 64, bias, relu);
+        conv1x1_dual_tile<1, 1, 32>(lds, t, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, relu);
     }
 }
 
@@ -241,12 +241,12 @@ static void launch_dual(const float* t, const float* x, int64_t M, const float* 
     tm.m_active = nullptr;
     tm.tiles_m = (int)((M + 64 * TM - 1) / (64 * TM));
     tm.tiles_n = (int)((N + 64 * TN - 1) / (64 * TN));
-    const int64_t split = (TM == 2 && TN == 2) ? gemm_tail_split_rows(M, N, 256 * ISX_WG_PER_CU_128) : 0;
+    const int64_t split = (TM == 2 && TN == 2) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
     if (split > 0) {
         TileMap small;
         small.m_active = nullptr;
         tm.tiles_m = (int)(split / 128);
-        small.tiles_m = (int)((M - split + 64 * ISX_TAIL_TM - 1) / (64 * ISX_TAIL_TM));
+        small.tiles_m = (int)((M - split + 63) / 64);
         small.tiles_n = (int)((N + 63) / 64);
         hipLaunchKernelGGL(conv1x1_dual_tail_kernel, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, t, x, M, w, N, g,
                            y, tm, small, split, bias, relu);
@@ -300,7 +300,7 @@ ISX_API int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, c
     // 1.71 / 1.78 / 1.76; 64->64 at 56x56 - / 1.89 / 1.85): 128x128 (+ 64x64 tail) wherever the grid fills the chip, the shape with the
     // fewest idle CUs below that (512->512 at 14x14 with 64 images: 1568 tiles of 64x64 are 1.02 rounds, 784 of 128x64 are 0.77)
     static const float eff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
-    int best = pick_tile_cfg(M, N, gemm_tail_split_rows(M, N, 256 * ISX_WG_PER_CU_128), eff3x3, 0xD, ISX_WG_PER_CU_128);
+    int best = pick_tile_cfg(M, N, gemm_tail_split_rows(M, N, 256 * kWgPerCu128), eff3x3, 0xD, kWgPerCu128);
     { const int fc_ = g_force_conv_cfg; if (fc_ == 0 || fc_ == 2 || fc_ == 3) best = fc_; }
     hipStream_t st = (hipStream_t)stream;
     switch (best) {
@@ -360,7 +360,7 @@ ISX_API int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_
     // measured at B = 1024 (ms, 128x128 / 128x64 / 64x64): layer 1 2.10 / 2.22 / 2.21, layer 2 2.64 / 2.68 / 2.84,
     // layer 3 2.54 / 2.54 / 2.75, layer 4 (50 k pixels) 2.55 / 2.48 / 2.72
     static const float eff_dual[4] = {0.92f, 0.0f, 0.885f, 0.85f};                         // layer 1-4 at B = 1024: 128x128 best, then 128x64, then 64x64
-    int best = pick_tile_cfg(M, N, gemm_tail_split_rows(M, N, 256 * ISX_WG_PER_CU_128), eff_dual, 0xD, ISX_WG_PER_CU_128);
+    int best = pick_tile_cfg(M, N, gemm_tail_split_rows(M, N, 256 * kWgPerCu128), eff_dual, 0xD, kWgPerCu128);
     { const int fc_ = g_force_conv_cfg; if (fc_ == 0 || fc_ == 2 || fc_ == 3) best = fc_; }
     hipStream_t st = (hipStream_t)stream;
     if (best == 0) launch_dual<2, 2, 16>(t, x, M, w_cat, N, g, y, bias, relu ? 1 : 0, st);
@@ -370,7 +370,7 @@ ISX_API int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_
     return ISX_OK;
 }
 
-// Debug / A-B hook (not declared in include/isx.h): force the conv3x3 tile shape (0, 2, 3), -1 = automatic.
+// Test hook (include/isx.h): force the conv3x3 tile shape (0, 2, 3), -1 = automatic.
 ISX_API void isx_debug_set_conv_cfg(int c) {
     isx::g_tail_split = (c != 7);        // 7 = automatic tile choice WITHOUT the 64x64 tails (A/B)
     g_force_conv_cfg = (c == 7) ? -1 : c;

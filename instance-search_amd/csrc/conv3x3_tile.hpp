@@ -17,19 +17,18 @@ struct Conv3x3Geom { int H, W, Cin, Ho, Wo, stride; };
 // lds: BK * (64 TM + 64 TN + 2 pads) floats
 // AHEAD2 (64x64 tiles only): operands requested two k-tiles ahead instead of one (16 more VGPRs: the fused expand kernel has them, the plain
 // 64x64 kernel at six workgroups per CU does not).
-// WM: waves along M (2: the 2x2 arrangement of every other kernel; 4: four waves stacked along the pixels, each TM x TN tiles of the FULL width)
 // CHUNK: terms per first-level chain of the two-level sum (gemm_tile.hpp; the inference trunk), 0 = one chain over all 9 Cin terms (gradients)
-template <int TM, int TN, int BK, bool AHEAD2 = false, int WM = 2, int CHUNK = kConvChunk>
+template <int TM, int TN, int BK, bool AHEAD2 = false, int CHUNK = kConvChunk>
 __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N,
                                                  const Conv3x3Geom& g, int64_t m0, int64_t n0, f32x16 (&acc)[TM][TN]) {
-    constexpr int WN = 4 / WM, BM = 32 * TM * WM, BN = 32 * TN * WN, LDA = BM + lds_pad(BK), LDB = BN + lds_pad(BK);
+    constexpr int BM = 64 * TM, BN = 64 * TN, LDA = BM + lds_pad(BK), LDB = BN + lds_pad(BK);
     constexpr int CH = BK / 4, NA = BM * CH / 256;
     float* As = lds;
     float* Bs = lds + BK * LDA;
     const int D = 9 * g.Cin;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave / WN, wn = wave % WN;
+    const int wm = wave / 2, wn = wave % 2;
     const int l31 = lane & 31, half = lane >> 5;
 
 #pragma unroll
@@ -91,7 +90,7 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     const int nk = D / BK;
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4 && ISX_PIN_KTILE;
+    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4;
     KtilePtrs<BK> pins;
     if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
     auto take_tot = [&]() {                       // the tile's value: the sum of the chunk sums
@@ -108,8 +107,6 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
         // requested TWO k-tiles ahead, in two staging register sets (+16 VGPRs; the LDS stays single-staged).  An even k-tile count only (Cin a
         // multiple of 64); one trip of the loop = two k-tiles = ONE chunk of the two-level sum.
         static_assert(!AHEAD2 || CHUNK % (2 * BK) == 0, "a chunk is a whole number of trips of the two-ahead loop");
-        f32x16 (*totp2)[TN] = nullptr;
-        if constexpr (CHUNK != 0) totp2 = tot;
         float4 ra1[NA], ra2[NA], rb2[BN * BK / 1024];
         auto stage = [&](float4 (&qa)[NA], float4 (&qb)[BN * BK / 1024], int kt) {
             load_a();
@@ -128,8 +125,8 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
         // undo the prefetch); those of the last trip point past the last tap / weight column -- range-checked buffer loads, values never used.
         for (int kt = 0; kt < nk; kt += 2) {
             stage(ra2, rb2, kt + 2);
-            if (CHUNK != 0 && (kt * BK) % (CHUNK ? CHUNK : 1) == 0)      // chunk start: C = 0 (interleaved fold: the previous chunk's chain is added in front of it)
-                mfma_ktile<TM, TN, BK, LDA, LDB, CHUNK != 0>(a_base, b_base, acc, ISX_FOLD_INTERLEAVE >= 2 ? totp2 : nullptr);
+            if (CHUNK != 0 && (kt * BK) % (CHUNK ? CHUNK : 1) == 0)      // chunk start: C = 0
+                mfma_ktile<TM, TN, BK, LDA, LDB, CHUNK != 0>(a_base, b_base, acc);
             else mfma_ktile<TM, TN, BK, LDA, LDB>(a_base, b_base, acc);
             __syncthreads();
             store_tile<BM, BK>(As, ra1);
@@ -143,12 +140,9 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
                 store_tile<BN, BK>(Bs, rb2);
                 __syncthreads();
             }
-            if constexpr (ISX_FOLD_INTERLEAVE < 2) {
-                if constexpr (CHUNK == 2 * BK) add_chunk<TM, TN>(tot, acc);
-                else if constexpr (CHUNK != 0) { if (((kt + 2) * BK) % CHUNK == 0 || kt + 2 >= nk) add_chunk<TM, TN>(tot, acc); }
-            }
+            if constexpr (CHUNK == 2 * BK) add_chunk<TM, TN>(tot, acc);
+            else if constexpr (CHUNK != 0) { if (((kt + 2) * BK) % CHUNK == 0 || kt + 2 >= nk) add_chunk<TM, TN>(tot, acc); }
         }
-        if constexpr (ISX_FOLD_INTERLEAVE >= 2 && CHUNK != 0) add_chunk<TM, TN>(tot, acc);      // the last chunk
         take_tot();
         return;
     }
@@ -181,11 +175,11 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     } else {
         for (int kt = 0; kt < nk;) {
             const int kend = kt + CHUNK / BK < nk ? kt + CHUNK / BK : nk;
-            body(kt++, std::true_type());                      // (interleaved fold: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
+            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
             for (; kt < kend; ++kt) body(kt, std::false_type());
-            if (!((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2)) add_chunk<TM, TN>(tot, acc);
+            if (!PINNED) add_chunk<TM, TN>(tot, acc);
         }
-        if ((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2) add_chunk<TM, TN>(tot, acc);       // the last chunk
+        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
     }
     take_tot();
 }

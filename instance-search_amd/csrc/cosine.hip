@@ -29,12 +29,6 @@
 
 namespace isx {
 
-#ifndef ISX_A_NT
-#define ISX_A_NT 0              // A/B (round 6): aux bits of the ACTIVATION operand loads of the convolution GEMM (2 = nt)
-#endif
-#ifndef ISX_ST_NT
-#define ISX_ST_NT 0             // A/B (round 6): aux bits of the convolution GEMM's output stores (2 = nt)
-#endif
 #ifndef ISX_STAMPS
 #define ISX_STAMPS 0            // lab builds only (tools/build_variant.sh stamps -DISX_STAMPS=1, tools/conv_phase_lab.py): wave 0 of every workgroup of the
 #endif                          // convolution GEMM records the shader clock at its phase boundaries into the buffer set by isx_debug_set_stamps
@@ -98,14 +92,14 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
     // larger convolution tiles: the residual of the WHOLE tile is requested in one go right behind the main loop, into the registers the first-level
     // chains leave free, and consumed tile by tile as it arrives -- one round trip instead of TM x TN serialised ones (gemm_tile.hpp, epilogue_fetch).
     // (Requested one k-tile earlier, under the last MFMAs, the 64 values of a 128x128 tile push the kernel past 256 VGPRs: 204 B of scratch.)
-    constexpr bool LATE_RES = (EPI == 2 && TM * TN == 4 && ISX_EPI_LOADS_FIRST && !ISX_EPI_LDS);       // (128x64 tiles at their 128-register bound: 24-112 B of scratch with it)
+    constexpr bool LATE_RES = (EPI == 2 && TM * TN == 4);       // (128x64 tiles at their 128-register bound: 24-112 B of scratch with it)
     float late_res[LATE_RES ? TM : 1][LATE_RES ? TN : 1][16];
     const float* res_ptr = (EPI == 2) ? reinterpret_cast<const float*>(gflag) : nullptr;
 
     float4 ra[BM * BK / 1024], rb[BN * BK / 1024];
     const int nk = (D + BK - 1) / BK;
     if (EPI == 2) ISX_STAMP(0);
-    load_tile<ALIGNED, BM, BK, (EPI == 2 ? ISX_A_NT : 0)>(Q, M, D, m0, 0, ra);
+    load_tile<ALIGNED, BM, BK>(Q, M, D, m0, 0, ra);
     load_tile<ALIGNED, BN, BK>(G, N, D, n0, 0, rb);
     store_tile<BM, BK>(As, ra);
     store_tile<BN, BK>(Bs, rb);
@@ -114,7 +108,7 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
 
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4 && ISX_PIN_KTILE;
+    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4;
     KtilePtrs<BK> pins;
     if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
 
@@ -125,7 +119,7 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
     auto body = [&](int kt, auto zero_c) {
         const bool more = (kt + 1 < nk);
         if (more) {
-            load_tile<ALIGNED, BM, BK, (EPI == 2 ? ISX_A_NT : 0)>(Q, M, D, m0, (kt + 1) * BK, ra);
+            load_tile<ALIGNED, BM, BK>(Q, M, D, m0, (kt + 1) * BK, ra);
             load_tile<ALIGNED, BN, BK>(G, N, D, n0, (kt + 1) * BK, rb);
         }
         mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
@@ -141,11 +135,11 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
     } else {
         for (int kt = 0; kt < nk;) {
             const int kend = kt + CHUNK / BK < nk ? kt + CHUNK / BK : nk;
-            body(kt++, std::true_type());                      // (interleaved fold: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
+            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
             for (; kt < kend; ++kt) body(kt, std::false_type());
-            if (!((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2)) add_chunk<TM, TN>(tot, acc);
+            if (!PINNED) add_chunk<TM, TN>(tot, acc);
         }
-        if ((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2) add_chunk<TM, TN>(tot, acc);       // the last chunk
+        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
     }
     if (EPI == 2) ISX_STAMP(2);
     // the TN bias values of this lane's columns BEFORE everything else of the epilogue: a bias load behind the residual requests would make the first
@@ -179,16 +173,6 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
                                       half, thr);
         return;
     }
-    if (EPI == 2 && TM * TN == 4 && ISX_EPI_LDS) {
-        // 128x128 convolution tiles: float4 epilogue through a wave-private LDS transpose (gemm_tile.hpp) when the shapes allow 16-B accesses
-        const float* res = reinterpret_cast<const float*>(gflag);
-        if ((N & 3) == 0 && (ldc & 3) == 0 && (((uintptr_t)C | (uintptr_t)(res ? res : C) | (uintptr_t)thr) & 15) == 0) {        // uniform
-            conv_epilogue_lds<TM, TN>(acc, lds + (threadIdx.x >> 6) * (32 * TM) * (32 * TN + 4), C, res, thr, ngrp, m0, M, n0, N, ldc, BM, wm_u * (32 * TM),
-                                      wn_u * (32 * TN), lane);
-            if (ISX_STAMPS) { ISX_STAMP(3); ISX_STAMP(4); ISX_STAMP_DRAIN(); ISX_STAMP(5); }      // (the LDS epilogue's residual wait is inside it: stamp 3 = 4)
-            return;
-        }
-    }
     if (EPI == 2) {
         // Convolution epilogue through BUFFER instructions: a wave-uniform descriptor of the tile's rows (clipped at row M by the
         // hardware), one 32-bit lane offset per 32x32 MFMA tile (a column >= N gets an offset outside the descriptor: its loads return
@@ -217,7 +201,7 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
                     else if (LATE_RES) { if (res) y += late_res[LATE_RES ? i : 0][LATE_RES ? j : 0][e]; }
                     else if (res) y += rv[e];
                     if (ngrp) y = fmaxf(y, 0.0f);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), rc, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * ldc * 4), ISX_ST_NT);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), rc, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * ldc * 4), 0);
                 }
             }
         }
@@ -282,13 +266,12 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
 // (convolution mode: two accumulator sets.  128x128 tiles: two workgroups per CU -- without the bound hipcc takes 296 registers and one fits;
 // the smaller tiles serve the HBM-bound layers and keep four -- unbounded, the 128x64 shape took 164 registers and lost a fifth on 256 -> 64 at 56x56)
 template <bool ALIGNED, int TM, int TN, int EPI, int BK>
-__global__ __launch_bounds__(256, EPI != 2 ? 1 : TM * TN == 4 ? ISX_WG_PER_CU_128 : 4) void cosine_gemm_kernel(const float* __restrict__ Q, int64_t M,
+__global__ __launch_bounds__(256, EPI != 2 ? 1 : TM * TN == 4 ? kWgPerCu128 : 4) void cosine_gemm_kernel(const float* __restrict__ Q, int64_t M,
                                                           const float* __restrict__ G, int64_t N, int D,
                                                           float* __restrict__ C, int64_t ldc, TileMap tm,
                                                           const float* __restrict__ thr, uint8_t* __restrict__ gflag,
                                                           int ngrp) {
-    constexpr int kStage = BK * (64 * TM + 64 * TN + 2 * lds_pad(BK)), kEpi = (EPI == 2 && TM * TN == 4 && ISX_EPI_LDS) ? epilogue_lds_floats<TM, TN>() : 0;
-    __shared__ float lds[kStage > kEpi ? kStage : kEpi];
+    __shared__ float lds[BK * (64 * TM + 64 * TN + 2 * lds_pad(BK))];
     int tile_m, tile_n;
     tile_of_block(tm, tile_m, tile_n);
     const int64_t m0 = (int64_t)tile_m * (64 * TM), n0 = (int64_t)tile_n * (64 * TN);
@@ -300,10 +283,10 @@ __global__ __launch_bounds__(256, EPI != 2 ? 1 : TM * TN == 4 ? ISX_WG_PER_CU_12
 // as 64x64 tiles in the same grid (see conv3x3_tail_kernel in conv.hip: a few 128x128 tiles alone on their CUs at the end of a launch of
 // three to twelve rounds cost 3-10 % of it).  Same arithmetic per output element.
 template <bool ALIGNED>
-__global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv1x1_tail_kernel(const float* __restrict__ Q, int64_t M, const float* __restrict__ G, int64_t N, int D,
+__global__ __launch_bounds__(256, kWgPerCu128) void conv1x1_tail_kernel(const float* __restrict__ Q, int64_t M, const float* __restrict__ G, int64_t N, int D,
                                                               float* __restrict__ C, int64_t ldc, TileMap tm_big, TileMap tm_small, int64_t m_split,
                                                               const float* __restrict__ bias, uint8_t* __restrict__ res, int relu) {
-    constexpr int kBig0 = 16 * (128 + 128 + 2 * lds_pad(16)), kEpi = ISX_EPI_LDS ? epilogue_lds_floats<2, 2>() : 0, kBig = kBig0 > kEpi ? kBig0 : kEpi;
+    constexpr int kBig = 16 * (128 + 128 + 2 * lds_pad(16));
     __shared__ float lds[kBig > kTailLdsFloats ? kBig : kTailLdsFloats];
     const int nbig = tm_big.tiles_m * tm_big.tiles_n;                 // a multiple of 8: a block's XCD is the same in both numberings
     int tile_m, tile_n;
@@ -312,107 +295,7 @@ __global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv1x1_tail_kernel(co
         cosine_gemm_tile<ALIGNED, 2, 2, 2, 16>(lds, Q, M, G, N, D, C, ldc, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, res, relu);
     } else {
         tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        cosine_gemm_tile<ALIGNED, ISX_TAIL_TM, 1, 2, 32>(lds, Q, M, G, N, D, C, ldc, m_split + (int64_t)tile_m * (64 * ISX_TAIL_TM), (int64_t)tile_n * 64, bias, res, relu);
-    }
-}
-
-// ---- PERSISTENT 128x128 tiles for the 1x1 convolutions (round 5) ----------------------------------------------------------------------------------
-// A short-K layer (K = 128 ... 512: 8 ... 32 k-tiles) pays the fill of its load pipeline once per TILE: the first k-tile's operands take an
-// HBM / L2 round trip (~2 us) before the first MFMA can issue, a quarter of a K = 128 tile's matrix time, and two workgroups per CU cannot
-// hide it for each other (128 -> 512 + residual at 28x28: 0.62 of its own roofline, neither HBM- nor MFMA-bound).  Here 512 workgroups
-// (two per CU) each walk tiles b, b + G, b + 2 G, ... of the same XCD-aware order, and the operands of the NEXT tile's first k-tile are
-// requested before the current tile's epilogue: they land while the epilogue's loads and stores are in flight.  The staging registers are
-// free at that point, so the prefetch costs none.  Same arithmetic per output element as cosine_gemm_tile<..., EPI 2>.
-// MEASURED: bit-identical and 4 % slower than one workgroup per tile (see launch_gemm_any): kept as an A/B (ISX_CONV_PERSIST=1), not dispatched.
-template <bool ALIGNED>
-__global__ __launch_bounds__(256, ISX_WG_PER_CU_128) void conv1x1_persist_kernel(const float* __restrict__ Q, int64_t M, const float* __restrict__ G, int64_t N, int D,
-                                                                                float* __restrict__ C, int64_t ldc, TileMap tm, int ntiles, TileMap tm_small,
-                                                                                int64_t m_split, const float* __restrict__ bias, const float* __restrict__ res,
-                                                                                int relu, int* __restrict__ tickets) {
-    // tickets != nullptr (ISX_CONV_PERSIST=2, round 6): the next tile is DRAWN, not strided -- one counter per XCD (8 ints, zeroed by the launcher), a
-    // workgroup on XCD x = blockIdx & 7 takes the next undone tile of x's own contiguous range, so that the dispatcher's dynamic balance is kept and the
-    // tiles of an XCD still share their operands in its L2.  The ticket is drawn at the top of a tile and has landed by its epilogue.
-    constexpr int TM = 2, TN = 2, BK = 16, BM = 128, BN = 128, LDA = BM + lds_pad(BK), LDB = BN + lds_pad(BK), CHUNK = kConvChunk;
-    __shared__ float lds[BK * (LDA + LDB)];
-    __shared__ int s_next;
-    float* As = lds;
-    float* Bs = lds + BK * LDA;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
-    const int wm_u = __builtin_amdgcn_readfirstlane(wm), wn_u = __builtin_amdgcn_readfirstlane(wn);
-    const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
-    const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = CHUNK != 0 && ISX_PIN_KTILE;
-    KtilePtrs<BK> pins;
-    if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
-    const int nk = (D + BK - 1) / BK;
-
-    float4 ra[BM * BK / 1024], rb[BN * BK / 1024];
-    int t = (int)blockIdx.x;
-    int tile_m = 0, tile_n = 0;
-    if (t < ntiles) {
-        tile_of_block(tm, tile_m, tile_n, t, ntiles);
-        load_tile<ALIGNED, BM, BK>(Q, M, D, (int64_t)tile_m * BM, 0, ra);
-        load_tile<ALIGNED, BN, BK>(G, N, D, (int64_t)tile_n * BN, 0, rb);
-    }
-    while (t < ntiles) {
-        const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-        f32x16 acc[TM][TN], tot[CHUNK ? TM : 1][CHUNK ? TN : 1];
-        zero_tiles(acc);
-        zero_tiles(tot);
-        int drawn = 0;                                                       // thread 0: requested now, consumed in the last k-tile (the atomic's round trip hides behind the main loop)
-        if (tickets && threadIdx.x == 0) drawn = atomicAdd(tickets + ((int)blockIdx.x & 7), 1);
-        store_tile<BM, BK>(As, ra);
-        store_tile<BN, BK>(Bs, rb);
-        __syncthreads();
-        f32x16 (*totp)[TN] = nullptr;
-        if constexpr (CHUNK != 0) totp = tot;
-        auto body = [&](int kt, auto zero_c) {
-            const bool more = (kt + 1 < nk);
-            if (more) {
-                load_tile<ALIGNED, BM, BK>(Q, M, D, m0, (kt + 1) * BK, ra);
-                load_tile<ALIGNED, BN, BK>(G, N, D, n0, (kt + 1) * BK, rb);
-            }
-            if (!more && tickets && threadIdx.x == 0) s_next = ((int)blockIdx.x & 7) + 8 * ((int)(gridDim.x >> 3) + drawn);       // published by the barrier below
-            mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
-            __syncthreads();
-            if (more) {
-                store_tile<BM, BK>(As, ra);
-                store_tile<BN, BK>(Bs, rb);
-                __syncthreads();
-            }
-        };
-        if constexpr (CHUNK == 0) {
-            for (int kt = 0; kt < nk; ++kt) body(kt, std::false_type());
-        } else {
-            for (int kt = 0; kt < nk;) {
-                const int kend = kt + CHUNK / BK < nk ? kt + CHUNK / BK : nk;
-                body(kt++, std::true_type());
-                for (; kt < kend; ++kt) body(kt, std::false_type());
-                if (!((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2)) add_chunk<TM, TN>(tot, acc);
-            }
-            if ((PINNED && ISX_FOLD_INTERLEAVE) || ISX_FOLD_INTERLEAVE >= 2) add_chunk<TM, TN>(tot, acc);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
-        }
-        // the next tile's first operands: on their way while this tile's epilogue runs (every wave has left the LDS: the loop ended on a barrier)
-        int tn = t + (int)gridDim.x;
-        if (tickets) tn = __builtin_amdgcn_readfirstlane(s_next);
-        if (tn < ntiles) {
-            tile_of_block(tm, tile_m, tile_n, tn, ntiles);
-            load_tile<ALIGNED, BM, BK>(Q, M, D, (int64_t)tile_m * BM, 0, ra);
-            load_tile<ALIGNED, BN, BK>(G, N, D, (int64_t)tile_n * BN, 0, rb);
-        }
-        conv_epilogue_buffers<TM, TN>(acc, C, res, bias, relu, m0, M, n0, N, ldc, BM, wm_u * (32 * TM), wn_u * (32 * TN), l31, half);
-        t = tn;
-    }
-    // rows past the last whole round of 128x128 tiles: 64x64 tiles (conv1x1_tail_kernel's scheme), spread over the same workgroups
-    const int nsmall = tm_small.tiles_m * tm_small.tiles_n;
-    for (int ts = (int)blockIdx.x; ts < nsmall; ts += (int)gridDim.x) {
-        tile_of_block(tm_small, tile_m, tile_n, ts, nsmall);
-        cosine_gemm_tile<ALIGNED, 1, 1, 2, 32>(lds, Q, M, G, N, D, C, ldc, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, (uint8_t*)res, relu);
+        cosine_gemm_tile<ALIGNED, 1, 1, 2, 32>(lds, Q, M, G, N, D, C, ldc, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, res, relu);
     }
 }
 
@@ -498,9 +381,9 @@ static int launch_gemm_any(const float* Q, int64_t M, const float* G, int64_t N,
     const bool aligned = (D % 32 == 0) && (((uintptr_t)Q | (uintptr_t)G) % 16 == 0);     // no k tail for BK = 16 or 32
     const bool aligned16 = aligned || ((D % 16 == 0) && (((uintptr_t)Q | (uintptr_t)G) % 16 == 0));   // enough for the BK = 16 (128x128) tiles: D = 464
     // convolutions: 128x128 tiles (two workgroups per CU: the two-level sum) + 64x64 tail in one grid
-    const int64_t split = (epi == 2) ? gemm_tail_split_rows(M, N, 256 * ISX_WG_PER_CU_128) : 0;
+    const int64_t split = (epi == 2) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
     static const float eff_gemm[4] = {kCfgs[0].eff, kCfgs[1].eff, kCfgs[2].eff, kCfgs[3].eff};
-    int best = pick_tile_cfg(M, N, split, eff_gemm, 0xF, epi == 2 ? ISX_WG_PER_CU_128 : 4);
+    int best = pick_tile_cfg(M, N, split, eff_gemm, 0xF, epi == 2 ? kWgPerCu128 : 4);
     // (Round 1 forced 64x64 tiles on residual layers and 128x64 on the others: the per-element epilogue was a visible share of a tile.
     // With the buffer-instruction epilogue the same round / tail model as for the score GEMM picks the convolution tiles: 128x128
     // wherever the grid fills the chip -- 256->1024 + residual 0.90 -> 0.87 ms, 512->2048 + residual 0.85 -> 0.81, 512->256 1.64 -> 1.58 --
@@ -521,36 +404,11 @@ static int launch_gemm_any(const float* Q, int64_t M, const float* G, int64_t N,
             return ISX_OK;
         }
     }
-    // A/B (round 5), OFF by default: persistent workgroups with the next tile's first operands prefetched across the epilogue are
-    // 4 % SLOWER on the ten 1x1 shapes of the lab (11.37 vs 10.90 ms; 128 -> 512 + residual 1.10 vs 1.07): the hardware dispatcher's dynamic
-    // placement of one workgroup per tile beats the static walk, and the pipeline fill of a tile is not what the short-K layers wait for.
-    static const int persist_mode = [] { const char* e = getenv("ISX_CONV_PERSIST"); return e ? atoi(e) : 0; }();      // 1 = strided tiles (round 5), 2 = drawn tiles (round 6)
-    static const bool use_persist = persist_mode == 1 || persist_mode == 2;
-    if (epi == 2 && best == 0 && use_persist && (g_force_cfg < 0 || g_force_cfg == 0)) {
-        TileMap tmap, small;
-        tmap.m_active = small.m_active = nullptr;
-        tmap.tiles_m = (int)((split > 0 ? split : M + 127) / 128); tmap.tiles_n = (int)((N + 127) / 128);
-        small.tiles_m = split > 0 ? (int)((M - split + 63) / 64) : 0; small.tiles_n = (int)((N + 63) / 64);
-        const int ntiles = tmap.tiles_m * tmap.tiles_n;
-        const int slots = 256 * ISX_WG_PER_CU_128;
-        const int want = ntiles + small.tiles_m * small.tiles_n;
-        const dim3 grid((unsigned)(want < slots ? want : slots)), block(256);
-        int* tickets = nullptr;
-        if (persist_mode == 2 && grid.x % 8 == 0) {                           // A/B only: the counters live in a lazily allocated device buffer, zeroed per launch
-            static int* g_tickets = nullptr;
-            if (!g_tickets && hipMalloc((void**)&g_tickets, 64) != hipSuccess) g_tickets = nullptr;
-            if (g_tickets && hipMemsetAsync(g_tickets, 0, 64, st) == hipSuccess) tickets = g_tickets;
-        }
-        if (aligned) hipLaunchKernelGGL((conv1x1_persist_kernel<true>), grid, block, 0, st, Q, M, G, N, D, C, ldc, tmap, ntiles, small, split, thr, (const float*)gmax, relu, tickets);
-        else hipLaunchKernelGGL((conv1x1_persist_kernel<false>), grid, block, 0, st, Q, M, G, N, D, C, ldc, tmap, ntiles, small, split, thr, (const float*)gmax, relu, tickets);
-        ISX_CHECK_LAUNCH("conv1x1_persist");
-        return ISX_OK;
-    }
     if (best == 0 && split > 0) {
         TileMap big, small;
         big.m_active = small.m_active = nullptr;
         big.tiles_m = (int)(split / 128); big.tiles_n = (int)((N + 127) / 128);
-        small.tiles_m = (int)((M - split + 64 * ISX_TAIL_TM - 1) / (64 * ISX_TAIL_TM)); small.tiles_n = (int)((N + 63) / 64);
+        small.tiles_m = (int)((M - split + 63) / 64); small.tiles_n = (int)((N + 63) / 64);
         const dim3 grid((unsigned)(big.tiles_m * big.tiles_n + small.tiles_m * small.tiles_n)), block(256);
         if (aligned) hipLaunchKernelGGL((conv1x1_tail_kernel<true>), grid, block, 0, st, Q, M, G, N, D, C, ldc, big, small, split, thr, gmax, relu);
         else hipLaunchKernelGGL((conv1x1_tail_kernel<false>), grid, block, 0, st, Q, M, G, N, D, C, ldc, big, small, split, thr, gmax, relu);
@@ -692,7 +550,7 @@ int run_topk_chunks(const TopkJob& j) {
 
 using namespace isx;
 
-// Debug / A-B hook (not declared in include/isx.h): force a tile shape (0..3), -1 = automatic.
+// Test hook (include/isx.h): force a tile shape (0..3), -1 = automatic.
 ISX_API void isx_debug_set_gemm_cfg(int c) { set_gemm_cfg(c); }
 
 ISX_API int isx_cosine_sim(const float* Q, int64_t M, const float* G, int64_t N, int D, float* sim, isx_stream_t stream) {

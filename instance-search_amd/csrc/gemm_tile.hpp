@@ -1,12 +1,6 @@
 // gemm_tile.hpp -- device helpers shared by the fp32-MFMA GEMM (cosine.hip) and the implicit-GEMM 3x3 convolution
 // (conv.hip): XCD-aware tile mapping and the K-major LDS staging of operand tiles.
 #pragma once
-#ifndef ISX_SIMPLE_KLOOP
-#define ISX_SIMPLE_KLOOP 0      // A/B: 1 = the plain per-step k loop on every tile shape
-#endif
-#ifndef ISX_KLOOP_PREFETCH
-#define ISX_KLOOP_PREFETCH 1    // A/B: 1 = operand fragments of k-step kk + 1 fetched before the MFMAs of step kk (large tiles; +0.7-1.5 % on the big GEMMs)
-#endif
 #include <type_traits>
 
 #include "isx_internal.hpp"
@@ -15,10 +9,7 @@ namespace isx {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-#ifndef ISX_GROUP_N
-#define ISX_GROUP_N 16
-#endif
-constexpr int GROUP_N = ISX_GROUP_N;            // n-tiles per scheduling group
+constexpr int GROUP_N = 16;                     // n-tiles per scheduling group
 
 struct TileMap {
     int tiles_m, tiles_n;
@@ -136,14 +127,6 @@ __device__ __forceinline__ unsigned conv_lane_off(int64_t ncol, int64_t N, int r
 }
 
 
-// Convolution epilogue of one wave's TM x TN accumulator tiles through BUFFER instructions: y = act(acc + bias[n] (+ residual)).
-// rc / rr: descriptors of the block tile's rows of C / the residual; row0 = the wave's first tile row (wave-uniform).
-#ifndef ISX_RES_NT
-#define ISX_RES_NT 0            // A/B: aux bits of the residual loads of the convolution epilogues (2 = nt: a residual is read once)
-#endif
-#ifndef ISX_EPI_LOADS_FIRST
-#define ISX_EPI_LOADS_FIRST 1   // A/B (round 6): 1 = every residual / mask value of the wave's TM x TN tiles requested before the first store
-#endif
 // lane offset and SGPR row offsets of the 16 C elements a lane holds of one 32x32 MFMA tile
 __device__ __forceinline__ constexpr int mfma_row_of(int e) { return (e & 3) + 8 * (e >> 2); }
 
@@ -163,7 +146,7 @@ __device__ __forceinline__ void epilogue_fetch(float (&rv)[TM][TN][16], const fl
             const unsigned lo = conv_lane_off(ncol, N, row0 + i * 32 + 4 * half, ldc);
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                rv[i][j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, lo, (unsigned)(mfma_row_of(e) * ldc * 4), ISX_RES_NT));
+                rv[i][j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, lo, (unsigned)(mfma_row_of(e) * ldc * 4), 0));
         }
 }
 
@@ -185,7 +168,7 @@ __device__ __forceinline__ void conv_epilogue_buffers(const f32x16 (&acc)[TM][TN
         const int ncol = (int)n0 + col0 + j * 32 + l31;
         bias_pre[j] = (bias && ncol < N) ? bias[ncol] : 0.0f;
     }
-    if (ISX_EPI_LOADS_FIRST && !(res && mask)) {
+    if (!(res && mask)) {
         // one operand stream besides the accumulators (residual OR mask, or none): fetch AHEAD tiles' worth, then add / select / store them
         constexpr int NT = TM * TN, STEP = AHEAD < 1 ? 1 : (AHEAD > NT ? NT : AHEAD);
         const float* src = res ? res : mask;
@@ -200,7 +183,7 @@ __device__ __forceinline__ void conv_epilogue_buffers(const f32x16 (&acc)[TM][TN
                     const unsigned lo = conv_lane_off((int)n0 + col0 + j * 32 + l31, N, row0 + i * 32 + 4 * half, ldc);
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
-                        rv[t - t0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, lo, (unsigned)(mfma_row_of(e) * ldc * 4), ISX_RES_NT));
+                        rv[t - t0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, lo, (unsigned)(mfma_row_of(e) * ldc * 4), 0));
                 }
                 __builtin_amdgcn_sched_barrier(0);           // keep the batch's loads above its first store
             }
@@ -253,51 +236,6 @@ __device__ __forceinline__ void conv_epilogue_buffers(const f32x16 (&acc)[TM][TN
     }
 }
 
-// Convolution epilogue through the LDS (round 5): the C layout of the 32x32 MFMA gives a lane ONE column and 16 scattered rows -- 4-byte stores,
-// a wave instruction covers 2 rows x 128 B.  Here every wave parks its TM x TN tiles in a wave-private LDS region as a row-major (32 TM) x
-// (32 TN) image and reads it back as float4 along the rows: residual loads and stores are 16 B per lane, a wave instruction covers 64 / (8 TN)
-// rows x 128 TN B -- a quarter of the memory instructions, twice the contiguous run.  The residual is requested before the transpose.
-// wl: this wave's (32 TM) x (32 TN + 4) floats (the +4 keeps rows 16-B aligned and the transposed reads conflict-light); needs N % 4 == 0,
-// ldc % 4 == 0 and 16-B aligned C / res (the caller checks); same arithmetic per element as conv_epilogue_buffers: y = act(acc + bias (+ res)).
-template <int TM, int TN>
-__device__ __forceinline__ void conv_epilogue_lds(const f32x16 (&acc)[TM][TN], float* __restrict__ wl, float* __restrict__ C, const float* __restrict__ res,
-                                                  const float* __restrict__ bias, int relu, int64_t m0, int64_t M, int64_t n0, int64_t N, int64_t ldc, int BM,
-                                                  int row0, int col0, int lane) {
-    constexpr int LDW = 32 * TN + 4, LPR = 8 * TN, RPI = 64 / LPR, NIT = 32 * TM / RPI;       // lanes per row, rows per instruction, instructions
-    const int l31 = lane & 31, half = lane >> 5;
-    const int r4 = lane / LPR, c4 = lane % LPR;
-    const auto rc = conv_tile_rsrc(C, m0, M, ldc, BM);
-    const auto rr = conv_tile_rsrc(res ? res : C, m0, M, ldc, BM);
-    const int64_t col = n0 + col0 + 4 * c4;
-    const unsigned lo = col < N ? (unsigned)(((row0 + r4) * ldc + col) * 4) : 0x80000000u;
-    float4 rv[NIT];
-    if (res) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it)
-            rv[it] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, lo, (unsigned)(it * RPI * ldc * 4), 0));
-    }
-    const float4 b4 = (bias && col < N) ? *reinterpret_cast<const float4*>(bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) wl[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * half) * LDW + j * 32 + l31] = acc[i][j][e];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        float4 v = *reinterpret_cast<const float4*>(wl + (it * RPI + r4) * LDW + 4 * c4);
-        v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
-        if (res) { v.x += rv[it].x; v.y += rv[it].y; v.z += rv[it].z; v.w += rv[it].w; }
-        if (relu) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rc, lo, (unsigned)(it * RPI * ldc * 4), 0);
-    }
-}
-template <int TM, int TN>
-constexpr int epilogue_lds_floats() { return 4 * (32 * TM) * (32 * TN + 4); }
-#ifndef ISX_EPI_LDS
-#define ISX_EPI_LDS 0        // A/B (round 5): float4 epilogue through an LDS transpose: bit-identical, NO gain (1x1 lab 10.96 vs 10.91 ms) -- store width is not what limits the short-K layers
-#endif
-
 // ---- two-level accumulation of the trunk convolutions (round 5) -----------------------------------------------------------------
 // A convolution output is NOT one fp32 chain over the whole reduction any more: the flattened reduction (kh, kw, ci) is cut into chunks of
 // ISX_CONV_CHUNK terms; inside a chunk the k-ordered fma chain of the matrix core starts from +0, and the chunk sums are added, in order, into
@@ -305,14 +243,9 @@ constexpr int epilogue_lds_floats() { return 4 * (32 * TM) * (32 * TN + 4); }
 // Why: a chain over K terms drifts from the exact sum like eps . K, chunks of c terms like eps . sqrt(K c + K^2 / c); measured end to end
 // (scratch/chunk_study.py, ResNet-50 / ResNet-152 descriptors against a float64 evaluation): one chain is 1.2x further from float64 than torch's
 // CPU fp32 path, chunks of 64 land at 0.7x.  K <= 64 (one chunk): tot = 0 + chain, the bits of rounds 1-4.  Restated by oracle/isx_oracle.c.
-#ifdef ISX_CONV_CHUNK_AB
-constexpr int kConvChunk = ISX_CONV_CHUNK_AB;      // A/B builds only (tools/build_variant.sh): the oracle follows ISX_CONV_CHUNK
-#else
 constexpr int kConvChunk = ISX_CONV_CHUNK;
-#endif
-#ifndef ISX_WG_PER_CU_128
-#define ISX_WG_PER_CU_128 2     // resident workgroups per CU of the 128x128 convolution tiles: two accumulator sets = 128 VGPRs + ~55 -> two waves per SIMD
-#endif
+constexpr int kWgPerCu128 = 2;      // resident workgroups per CU of the 128x128 convolution tiles: two accumulator sets = 128 VGPRs + ~55 -> two waves per SIMD
+constexpr int kTailLdsFloats = 32 * (64 + 64 + 2);      // BK = 32 stage of a 64x64 tail tile of the 128x128 convolution launches (lds_pad(32) = 1 per operand)
 static_assert(kConvChunk % 32 == 0, "a chunk is a whole number of k-tiles");
 
 // tot += acc (the chain of the chunk that just ended; acc itself is overwritten by the first MFMAs of the next chunk, which take C = 0)
@@ -342,9 +275,9 @@ __device__ __forceinline__ void add_tile_inplace(f32x16& a, const f32x16& t) {
 // of a drain per step; +4 % on the trunk's 1x1 convolutions).  a_base / b_base: this lane's first operand element.
 // ZERO_C: the first k-step starts new chains (C = 0 as an inline constant; the old contents of acc are dead): chunk start of the two-level sum.
 template <int TM, int TN, int BK, int LDA, int LDB, bool ZERO_C = false>
-__device__ __forceinline__ void mfma_ktile(const float* __restrict__ a_base, const float* __restrict__ b_base, f32x16 (&acc)[TM][TN], f32x16 (*tot)[TN] = nullptr) {
+__device__ __forceinline__ void mfma_ktile(const float* __restrict__ a_base, const float* __restrict__ b_base, f32x16 (&acc)[TM][TN]) {
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (TM * TN <= 2 && !ISX_SIMPLE_KLOOP) {
+    if (TM * TN <= 2) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             float af[BK / 4][TM], bf[BK / 4][TN];
@@ -360,14 +293,13 @@ __device__ __forceinline__ void mfma_ktile(const float* __restrict__ a_base, con
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        if (ZERO_C && h == 0 && kk == 0 && tot) add_tile_inplace(tot[i][j], acc[i][j]);
+                    for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][i], bf[kk][j], (ZERO_C && h == 0 && kk == 0) ? zero : acc[i][j], 0, 0, 0);
-                    }
         }
-    } else if (ISX_KLOOP_PREFETCH) {
+    } else {
         // register prefetch one k-step ahead: the operand reads of step kk + 1 are issued BEFORE the MFMAs of step kk, so a wave
-        // that finds itself alone on its SIMD (siblings parked at a barrier) does not expose an LDS round trip per step
+        // that finds itself alone on its SIMD (siblings parked at a barrier) does not expose an LDS round trip per step (+0.7-1.5 % on the big GEMMs
+        // against the plain per-step loop)
         float a[2][TM], b[2][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) a[0][i] = a_base[32 * i];
@@ -385,26 +317,8 @@ __device__ __forceinline__ void mfma_ktile(const float* __restrict__ a_base, con
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (ZERO_C && kk == 0 && tot) add_tile_inplace(tot[i][j], acc[i][j]);
+                for (int j = 0; j < TN; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk & 1][i], b[kk & 1][j], (ZERO_C && kk == 0) ? zero : acc[i][j], 0, 0, 0);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk) {
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = a_base[(2 * kk) * LDA + 32 * i];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = b_base[(2 * kk) * LDB + 32 * j];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (ZERO_C && kk == 0 && tot) add_tile_inplace(tot[i][j], acc[i][j]);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], (ZERO_C && kk == 0) ? zero : acc[i][j], 0, 0, 0);
-                }
         }
     }
 }
@@ -414,13 +328,6 @@ __device__ __forceinline__ void mfma_ktile(const float* __restrict__ a_base, con
 // addresses once; with the chunk fold in the loop it re-derived them with a v_add_u32 in front of every ds_read2 instead (15 VALU instructions
 // among the 32 MFMAs of a k-tile; the two-level kernels ran 10 % below the one-chain ones at ANY chunk length).  The empty asm makes each
 // address an opaque 32-bit LDS pointer that cannot be rematerialised.
-#ifndef ISX_TAIL_TM
-#define ISX_TAIL_TM 1           // tail tiles of the 128x128 convolution launches: 64 ISX_TAIL_TM rows x 64 columns (A/B: 2)
-#endif
-constexpr int kTailLdsFloats = 32 * (64 * ISX_TAIL_TM + 64 + 2);      // BK = 32 stage of a tail tile (lds_pad(32) = 1 per operand)
-#ifndef ISX_PIN_KTILE
-#define ISX_PIN_KTILE 1
-#endif
 using lds_cfp = const __attribute__((address_space(3))) float*;
 template <int BK>
 struct KtilePtrs { lds_cfp a[BK / 2], b[BK / 2]; };
@@ -437,7 +344,7 @@ __device__ __forceinline__ KtilePtrs<BK> pin_ktile_ptrs(const float* a_base, con
     return p;
 }
 // the k loop of mfma_ktile's prefetch variant on pinned addresses
-// tot (ZERO_C only, ISX_FOLD_INTERLEAVE): the chain that ended with the previous k-tile is added to tot tile by tile right in front of the MFMA that
+// tot (ZERO_C only): the chain that ended with the previous k-tile is added to tot tile by tile right in front of the MFMA that
 // restarts that tile from C = 0 -- the adds of tile n + 1 issue while the MFMA of tile n runs.  (The MFMAs that produced acc are at least one
 // barrier old: no MFMA -> VALU wait states needed.)
 template <int TM, int TN, int BK, bool ZERO_C = false>
@@ -490,14 +397,11 @@ __device__ __forceinline__ void fold_chunk(f32x16 (&tot)[TM][TN], f32x16 (&acc)[
     add_chunk<TM, TN>(tot, acc);
     zero_tiles(acc);
 }
-#ifndef ISX_FOLD_INTERLEAVE
-#define ISX_FOLD_INTERLEAVE 1
-#endif
-// returns true when the k-tile added the previous chunk's chain to tot itself (pinned 128x128 shape with ISX_FOLD_INTERLEAVE)
+// PINNED (the 128x128 shape): the k-tile adds the previous chunk's chain to tot itself; otherwise the caller folds with add_chunk behind the chunk
 template <int TM, int TN, int BK, int LDA, int LDB, bool PINNED, bool ZERO_C = false>
 __device__ __forceinline__ void mfma_ktile_sel(const float* __restrict__ a_base, const float* __restrict__ b_base, const KtilePtrs<BK>& pins, f32x16 (&acc)[TM][TN],
                                                f32x16 (*tot)[TN] = nullptr) {
-    if constexpr (PINNED) mfma_ktile_pinned<TM, TN, BK, ZERO_C>(pins, acc, ISX_FOLD_INTERLEAVE ? tot : nullptr);
-    else mfma_ktile<TM, TN, BK, LDA, LDB, ZERO_C>(a_base, b_base, acc, ISX_FOLD_INTERLEAVE >= 2 ? tot : nullptr);
+    if constexpr (PINNED) mfma_ktile_pinned<TM, TN, BK, ZERO_C>(pins, acc, tot);
+    else mfma_ktile<TM, TN, BK, LDA, LDB, ZERO_C>(a_base, b_base, acc);
 }
 }  // namespace isx

@@ -36,22 +36,8 @@ static int head_splits(int64_t K) {
 // read once instead of once per 64 rows; the tile shape only groups outputs, every output is the same chain in any of them.
 // ROWS: x is given as stored, (M, K) row-major (xT = x, Mrows = M): its tiles take the transposing LDS store of the weight tiles; rows past M read
 // zeros through the buffer descriptor.  Otherwise xT is (K, Mp), K-major, and goes to the LDS as it lies.  Same chain per output either way.
-#ifndef ISX_LB_HEADFWD
-#define ISX_LB_HEADFWD 2
-#endif
-#ifndef ISX_SGD_AHEAD
-#define ISX_SGD_AHEAD 1         // MFMA tiles of the fused gradient + SGD kernel whose w / momentum values are requested before the first store.  MEASURED (round 6,
-                                // tools/head_lab.py, 192 x 100352 x 2048): 1 tile / 3 workgroups per CU 0.954 ms (3.45 TB/s), 2 tiles / 3 WG 0.957, all 4 tiles / 2 WG 0.996 --
-                                // bytes in flight are not what holds the kernel at 3.4 TB/s (torch's fused elementwise SGD moves the same read + write mix at 3.7)
-#endif
-#ifndef ISX_SGD_NT
-#define ISX_SGD_NT 2            // (0.957 -> 0.932 ms, round 6; A/B: 0) aux bits of the w / momentum loads and stores of the fused SGD epilogue (2 = nt: read once, written once per step)
-#endif
-#ifndef ISX_LB_SGD
-#define ISX_LB_SGD 3
-#endif
 template <int TM, int TN = 1, bool ROWS = false>
-__global__ __launch_bounds__(256, TM * TN >= 6 ? ISX_LB_HEADFWD : TM * TN >= 3 ? 3 : 4) void head_fwd_gemm_kernel(const float* __restrict__ xT, int Mp, const float* __restrict__ Wn, int N, int K, int kt_per,
+__global__ __launch_bounds__(256, TM * TN >= 6 ? 2 : TM * TN >= 3 ? 3 : 4) void head_fwd_gemm_kernel(const float* __restrict__ xT, int Mp, const float* __restrict__ Wn, int N, int K, int kt_per,
                                                             float* __restrict__ part, int tiles_m, int Mrows = 0) {
     constexpr int BK = kHeadBK, BM = 64 * TM, BN = 64 * TN, LDA = ROWS ? BM + lds_pad(BK) : BM + 4, LDB = BN + lds_pad(BK);
     constexpr int CA = BM / 4, NA = ROWS ? BM * BK / 1024 : BK * CA / 256;
@@ -155,10 +141,15 @@ __global__ __launch_bounds__(256) void head_reduce_kernel(const float* __restric
 //   g += weight_decay * w;   buf = first ? g : momentum * buf + (1 - dampening) * g;   w -= lr * (nesterov ? g + momentum * buf : buf)
 // Tile 128 x 128 of the (N, K) weight per workgroup, R reduced in k-tiles of 32 rows (a tail of rows is zero-filled: fma(0, 0, acc) = acc).
 struct SgdParams { float lr, momentum, dampening, weight_decay; int nesterov, first, use_momentum; };
+// MFMA tiles of the fused gradient + SGD kernel whose w / momentum values are requested before the first store.  MEASURED (round 6, tools/head_lab.py,
+// 192 x 100352 x 2048): 1 tile / 3 workgroups per CU 0.954 ms (3.45 TB/s), 2 tiles / 3 WG 0.957, all 4 tiles / 2 WG 0.996 -- bytes in flight are not what
+// holds the kernel at 3.4 TB/s (torch's fused elementwise SGD moves the same read + write mix at 3.7)
+constexpr int kSgdAhead = 1;
+constexpr int kSgdNt = 2;       // aux bits of the w / momentum loads and stores of the fused SGD epilogue (2 = nt: read once, written once per step; 0.957 -> 0.932 ms, round 6)
 
 // TM: 128 (2) or 64 (1) rows of the weight per tile -- a shard of a sharded head can be as narrow as 64 output features; the tile only groups outputs
 template <int TM>
-__global__ __launch_bounds__(256, ISX_LB_SGD) void head_sgd_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t R, int N, int64_t K,
+__global__ __launch_bounds__(256, 3) void head_sgd_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t R, int N, int64_t K,
                                                        float* __restrict__ w, float* __restrict__ mom, SgdParams sp, int tiles_k) {
     constexpr int TN = 2, BK = 32, BM = 64 * TM, BN = 128, LDA = BM + 4, LDB = BN + 4;
     constexpr int CA = BM / 4, CB = BN / 4, NA = BK * CA / 256, NB = BK * CB / 256;
@@ -225,9 +216,10 @@ __global__ __launch_bounds__(256, ISX_LB_SGD) void head_sgd_kernel(const float* 
     // into the tile's rows of w / mom (buffer instructions: rows past N and columns past K fall outside the descriptor).
     // The kernel is HBM-bound (w and momentum read + written: 3.3 GB per step): what it needs is BYTES IN FLIGHT.  Round 5 read and wrote one MFMA
     // tile at a time -- 16 + 16 loads, a wait for them AND for the previous tile's stores (one counter on gfx9), 32 stores -- i.e. 8 KB in flight per
-    // wave and four load + store round trips per workgroup.  ISX_SGD_AHEAD tiles (default: all TM x TN) are requested before the first store.
+    // wave and four load + store round trips per workgroup.  kSgdAhead tiles are requested before the first store.
     const float one_minus_damp = 1.0f - sp.dampening;
-    constexpr int NT = TM * TN, STEP = ISX_SGD_AHEAD < 1 ? 1 : (ISX_SGD_AHEAD > NT ? NT : ISX_SGD_AHEAD);
+    constexpr int NT = TM * TN, STEP = kSgdAhead;
+    static_assert(STEP >= 1 && STEP <= NT, "kSgdAhead: 1 .. TM x TN tiles");
     const bool need_m = sp.use_momentum && !sp.first;
 #pragma unroll
     for (int t0 = 0; t0 < NT; t0 += STEP) {
@@ -238,7 +230,7 @@ __global__ __launch_bounds__(256, ISX_LB_SGD) void head_sgd_kernel(const float* 
             const int64_t col = k0 + wn_u * (32 * TN) + j * 32 + l31;
             const unsigned lo = conv_lane_off(col, K, wm_u * (32 * TM) + i * 32 + 4 * half, K);
 #pragma unroll
-            for (int e = 0; e < 16; ++e) wv[t - t0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), ISX_SGD_NT));
+            for (int e = 0; e < 16; ++e) wv[t - t0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), kSgdNt));
         }
         if (need_m) {
 #pragma unroll
@@ -247,7 +239,7 @@ __global__ __launch_bounds__(256, ISX_LB_SGD) void head_sgd_kernel(const float* 
                 const int64_t col = k0 + wn_u * (32 * TN) + j * 32 + l31;
                 const unsigned lo = conv_lane_off(col, K, wm_u * (32 * TM) + i * 32 + 4 * half, K);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) mv[t - t0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmom, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), ISX_SGD_NT));
+                for (int e = 0; e < 16; ++e) mv[t - t0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmom, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), kSgdNt));
             }
         }
         __builtin_amdgcn_sched_barrier(0);                   // the batch's loads above its first store
@@ -263,11 +255,11 @@ __global__ __launch_bounds__(256, ISX_LB_SGD) void head_sgd_kernel(const float* 
                 float upd = g;
                 if (sp.use_momentum) {
                     const float buf = sp.first ? g : sp.momentum * mv[t - t0][e] + one_minus_damp * g;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, buf), rmom, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), ISX_SGD_NT);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, buf), rmom, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), kSgdNt);
                     upd = sp.nesterov ? g + sp.momentum * buf : buf;
                 }
                 const float nw = wv[t - t0][e] - sp.lr * upd;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, nw), rw, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), ISX_SGD_NT);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, nw), rw, lo, (unsigned)(((e & 3) + 8 * (e >> 2)) * K * 4), kSgdNt);
             }
         }
     }
@@ -350,8 +342,7 @@ ISX_API int isx_head_linear_fwd(const float* xT, int64_t M, int64_t Mp, int64_t 
     ISX_REQUIRE(ws_bytes >= (size_t)S * (size_t)Mp * (size_t)N * 4, "isx_head_linear_fwd: workspace of %zu bytes, need %zu", ws_bytes, (size_t)S * (size_t)Mp * (size_t)N * 4);
     const int nk = (int)(K / kHeadBK), kt_per = (nk + S - 1) / S;
     hipStream_t st = (hipStream_t)stream;
-    static const bool wide = [] { const char* e = getenv("ISX_HEAD_WIDE"); return !(e && e[0] == '0'); }();      // A/B: 192 x 128 tiles (default) vs 192 x 64
-    if (Mp == 192 && N % 128 == 0 && wide)
+    if (Mp == 192 && N % 128 == 0)
         hipLaunchKernelGGL((head_fwd_gemm_kernel<3, 2>), dim3((unsigned)(N / 128), (unsigned)S), dim3(256), 0, st, xT, (int)Mp, w, N, (int)K, kt_per, ws, 1);
     else if (Mp == 192)
         hipLaunchKernelGGL(head_fwd_gemm_kernel<3>, dim3((unsigned)(N / 64), (unsigned)S), dim3(256), 0, st, xT, (int)Mp, w, N, (int)K, kt_per, ws, 1);

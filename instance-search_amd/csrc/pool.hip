@@ -163,12 +163,8 @@ __global__ __launch_bounds__(kGapThreads) void gap_l2_kernel(const float* __rest
 // 16-B loads (fully coalesced rows of C floats; no LDS needed), so the pooled values have the same
 // summation order as the NCHW kernel and the oracle.
 constexpr int kNhwcThreads = 512;
-#ifndef ISX_GAP_UNROLL
-#define ISX_GAP_UNROLL 7        // positions requested per thread before the first is added (A/B)
-#endif
-#ifndef ISX_GAP_NT_BYTES
-#define ISX_GAP_NT_BYTES (192ll << 20)     // maps above this size are read with NON-TEMPORAL loads (isx_gap_l2_nhwc); A/B: 0 = always, a huge value = never
-#endif
+constexpr int kGapUnroll = 7;                   // positions requested per thread before the first is added
+constexpr int64_t kGapNtBytes = 192ll << 20;    // maps above this size are read with NON-TEMPORAL loads (isx_gap_l2_nhwc; measurement below)
 
 // NT: the map is read with non-temporal loads.  A map that cannot stay in the 256 MB Infinity Cache anyway (the bench step's 1024 x 2048 x 7 x 7 is
 // 401 MB) streams through faster when its lines are not allocated on the way: 73.8 -> 62.8 us back to back = 5.7 -> 6.7 TB/s (0.71 -> 0.83 of 8 TB/s), and
@@ -183,7 +179,7 @@ __global__ __launch_bounds__(kNhwcThreads) void gap_l2_nhwc_kernel(const float* 
     float4 acc[QPT];
 #pragma unroll
     for (int q = 0; q < QPT; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll ISX_GAP_UNROLL
+#pragma unroll kGapUnroll
     for (int p = 0; p < HW; ++p) {
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
@@ -419,7 +415,7 @@ ISX_API int isx_gap_l2_nhwc(const float* fmap, int64_t B, int C, int H, int W, f
         return launch_l2norm(y, nullptr, B, C, eps, y, st);
     }
     const int nq = C / 4;
-    const bool nt = (int64_t)B * C * HW * 4 > (int64_t)ISX_GAP_NT_BYTES;
+    const bool nt = (int64_t)B * C * HW * 4 > kGapNtBytes;
     const dim3 grid((unsigned)B), block(kNhwcThreads);
     if (nq <= kNhwcThreads) {
         if (nt) hipLaunchKernelGGL((gap_l2_nhwc_kernel<1, true>), grid, block, 0, st, fmap, C, HW, eps, y);

@@ -90,8 +90,12 @@ _SIGNATURES = {
     "isx_comm_destroy": (C.c_int, [VP]),
     "isx_shard_topk_allgather": (C.c_int, [VP, VP, VP, I64, I32, VP, VP, VP]),
     "isx_comm_allgather_rows": (C.c_int, [VP, VP, I64, I64, VP, VP]),
+    # test hooks (process-global; end of include/isx.h)
+    "isx_debug_set_gemm_cfg": (None, [I32]),
+    "isx_debug_set_conv_cfg": (None, [I32]),
+    "isx_debug_set_f16_tile": (None, [I32]),
+    "isx_debug_fast_fallback_rows": (C.c_int, [VP, I64, I64, I32, I32, I32]),
 }
-
 EXPORTS = tuple(sorted(_SIGNATURES))
 
 

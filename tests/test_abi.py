@@ -2,6 +2,8 @@
 include/isx.h declares; argument validation works without touching a GPU."""
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -23,6 +25,18 @@ def test_header_symbols_exported():
         assert hasattr(lib, n), "libisx.so does not export %s" % n
     assert sorted(_lib.EXPORTS) == names, "binding table and header disagree"
     assert lib.isx_version() >= 100
+
+
+def test_exports_equal_declarations():
+    """Every isx_* symbol of the default build is declared in include/isx.h (no undeclared entry points)."""
+    from isx import _lib
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("nm not available")
+    _lib.lib()
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted({f[2] for f in (ln.split() for ln in out.splitlines()) if len(f) == 3 and f[2].startswith("isx_")})
+    assert exported == _declared()
 
 
 def test_argument_validation_without_gpu():

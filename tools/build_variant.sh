@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B builds of libisx.so with extra -D flags: tools/build_variant.sh <name> [-DISX_CONV_CHUNK_AB=128 ...]  ->  build_ab/<name>/libisx.so
+# A/B builds of libisx.so with extra -D flags: tools/build_variant.sh <name> [-DISX_STAMPS=1 ...]  ->  build_ab/<name>/libisx.so
 # (in-tree so that the library travels to the GPU box; select it with ISX_LIB=build_ab/<name>/libisx.so)
 set -e
 NAME=$1; shift

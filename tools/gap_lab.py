@@ -1,5 +1,5 @@
 """Times isx_gap_l2 on the trunk output of the bench step (B x 2048 x 7 x 7, channels-last) through the library named by ISX_LIB: us, GB/s of
-the algorithmic bytes (409 600 B per image), fraction of 8 TB/s.  For A/B builds (tools/build_variant.sh -DISX_GAP_UNROLL=.. -DISX_GAP_NT=1)."""
+the algorithmic bytes (409 600 B per image), fraction of 8 TB/s.  For A/B builds (tools/build_variant.sh; the tuning constants are kGapUnroll / kGapNtBytes in csrc/pool.hip)."""
 import os
 import sys
 
