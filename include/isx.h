@@ -16,11 +16,8 @@
  *     declared here: safe to capture in a hipGraph and re-entrant from several host
  *     threads on distinct streams (the test hooks at the end of this file are the
  *     exception)
- *   - environment, read once per process, tuning only (no value changes a result):
- *     ISX_TAIL_SPLIT=0 (128x128 grids without the 64x64 tail), ISX_TOPK_CHUNK_MB
- *     (score-chunk budget of the running top-k, default 1024), ISX_TOPK_FIRST
- *     (bootstrap chunk, default 8192 columns), ISX_FAST_KL_PCT (candidates kept per
- *     query by the fp16 filter, in % of k, default 200)
+ *   - the library reads no environment except the initial values of the test hooks
+ *     (ISX_DEBUG_GEMM_CFG, ISX_DEBUG_CONV_CFG; see the end of this file)
  *   - return 0 = ISX_OK, <0 = error; isx_last_error() gives a thread-local message
  *   - canonical ranking order everywhere: (score DESCENDING, index ASCENDING),
  *     -0.0 == +0.0; gallery indices must be < 2^32

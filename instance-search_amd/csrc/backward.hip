@@ -4,7 +4,7 @@
 // GEMM loops: ~150 launches per micro-batch).  Forward reuses the inference kernels with the BatchNorm folded into the
 // convolution (conv.hip); this file adds
 //
-//   isx_conv1x1_dgrad_nhwc   dX = (dZ . W' (+ add)) (. [mask > 0])     the NT GEMM of cosine.hip, epilogue mode 3
+//   isx_conv1x1_dgrad_nhwc   dX = (dZ . W' (+ add)) (. [mask > 0])     the NT GEMM of gemm.hip, epilogue kEpiMaskedGrad
 //   isx_conv3x3_dgrad_nhwc   the same for a 3x3 convolution: conv3x3 of dZ with the flipped / transposed weight, mask epilogue
 //   isx_conv_wgrad_nhwc      dW'[co][tap][ci] = sum_p dZ[p][co] * X[src(p, tap)][ci]   (1x1, strided 1x1 and 3x3: a TN GEMM over the
 //                            pixels; both operands are K-major in memory, so tiles go to LDS without a transpose)
@@ -20,8 +20,6 @@
 #include "wgrad_kernel.hpp"
 
 namespace isx {
-
-int launch_gemm_masked(const float* A, int64_t M, const float* Bt, int64_t N, int D, float* C, const float* mask, const float* add, hipStream_t st);
 
 // Number of pixel splits of a weight-gradient launch -- a function of the SHAPE only, so the summation tree of a micro-batch is the same whatever
 // runs around it (a rank with one micro-batch and a process with eight land on the same bits).

@@ -1,14 +1,14 @@
 // conv.hip -- convolutions of the inference trunk on channels-last activations (model/nn_utils.py fold_batch_norm).
 //
 //   isx_conv1x1_nhwc   the activation matrix (B*H*W, Cin) IS the row-major A operand of the fp32-MFMA GEMM of
-//                      cosine.hip; this file only adds the entry point (epilogue mode 2 of cosine_gemm_kernel)
+//                      gemm.hip; this file only adds the entry point (epilogue kEpiConv of cosine_gemm_kernel)
 //   isx_conv3x3_nhwc        implicit GEMM below (conv3x3_nhwc_kernel)
 //   isx_conv1x1_dual_nhwc   last 1x1 convolution of a bottleneck block + its projection shortcut as ONE GEMM over the
 //                           concatenated K = [t ; x_strided] (conv1x1_dual_nhwc_kernel)
 //   (expand.hip: isx_conv3x3_expand_nhwc / isx_conv3x3_expand_dual_nhwc, conv2 + conv3 (+ projection) of the 64-channel bottlenecks as ONE kernel,
 //    on the main loop of conv3x3_tile.hpp)
 // Launches in 128x128 tiles run the rows past their last whole round of resident workgroups as 64x64 tiles in the same grid
-// (conv3x3_tail_kernel, conv1x1_dual_tail_kernel; conv1x1_tail_kernel in cosine.hip); isx_debug_set_conv_cfg(7) turns that off (A/B).
+// (conv3x3_tail_kernel, conv1x1_dual_tail_kernel; conv1x1_tail_kernel in gemm.hip); isx_debug_set_conv_cfg(7) turns that off (A/B).
 //
 // Reference call sites: the torchvision ResNet `features` trunk built by model/ModelDefinition.py, split by
 // model/nn_utils.py:56-71 and run from model/siamese.py:20,107,151.

@@ -1,5 +1,5 @@
 // expand.hip -- conv2 + conv3 (+ projection) of the 64-channel bottlenecks as ONE kernel (isx_conv3x3_expand_nhwc, isx_conv3x3_expand_dual_nhwc).
-// A translation unit of its own: conv.hip and cosine.hip are compiled with the max-ILP scheduling strategy, which suits their plain tile loops
+// A translation unit of its own: conv.hip and gemm.hip are compiled with the max-ILP scheduling strategy, which suits their plain tile loops
 // (-0.3 ms each on the bench) and costs this kernel 4 % (Makefile).
 // Reference call sites: the torchvision ResNet `features` trunk built by model/ModelDefinition.py, split by model/nn_utils.py:56-71 and run from
 // model/siamese.py:20,107,151.

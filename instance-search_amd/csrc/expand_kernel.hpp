@@ -27,8 +27,7 @@ __global__ __launch_bounds__(256, DUAL ? 2 : 4) void conv3x3_expand_kernel(const
     static_assert(TILE_F >= 64 * LDY, "mid tile must fit the operand stages");
     // XCD-aware order: XCD x gets a contiguous range of pixel tiles (neighbouring tiles share their halo rows in its L2)
     const int nwg = (int)gridDim.x, b = (int)blockIdx.x;
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    const int64_t m0 = (int64_t)((xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3)) * 64;
+    const int64_t m0 = (int64_t)xcd_remap(b, nwg) * 64;
 
     // STAMPS (scratch/lab/expand_lab.hip only): shader-clock stamps of wave 0 at the phase boundaries, 8 per workgroup
     auto stamp = [&](int i) { if (STAMPS && threadIdx.x == 0) stamps[(int64_t)blockIdx.x * 8 + i] = __builtin_amdgcn_s_memtime(); };

@@ -196,8 +196,7 @@ __global__ __launch_bounds__(256) void cosine_gemm_f16_kernel(const _Float16* __
     char* Bs = lds + HTILE_B;
     // XCD-aware bijective remap + 16-wide n groups (as the fp32 kernel)
     const int nwg = tiles_m * tiles_n;
-    const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, nwg);
     const int per_group = 16 * tiles_m, gid = wg / per_group, first_n = gid * 16;
     const int gsz = min(16, tiles_n - first_n), within = wg - gid * per_group;
     const int64_t m0 = (int64_t)(within / gsz) * 128, n0 = (int64_t)(first_n + within % gsz) * 128;
@@ -301,8 +300,7 @@ __global__ __launch_bounds__(512) void cosine_gemm_f16_big_kernel(const _Float16
     __shared__ __attribute__((aligned(16))) char S0[GSTAGE_B];
     __shared__ __attribute__((aligned(16))) char S1[GSTAGE_B];
     const int nwg = tiles_m * tiles_n;
-    const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, nwg);
     constexpr int GN = 8;
     const int per_group = GN * tiles_m, gid = wg / per_group, first_n = gid * GN;
     const int gsz = min(GN, tiles_n - first_n), within = wg - gid * per_group;
@@ -440,14 +438,6 @@ __global__ __launch_bounds__(512) void cosine_gemm_f16_big_kernel(const _Float16
 //    re-staged only after a barrier that follows the lgkmcnt(0) of both wave groups' reads of it (WAR).
 // Measured (10 240 x 16 384, plain store): 1 204 TFLOP/s at D = 2048 and 1 370 at D = 4096 against 861 / 1 020 for 2b; the k loop
 // itself runs at ~1.3 us per k-tile (1 650 TFLOP/s), the rest is the output burst of the plain-store epilogue.
-// raw buffer descriptor from wave-uniform inputs (see gemm_tile.hpp uniform_rsrc; repeated here: fast.hip does not include it)
-__device__ __forceinline__ auto uniform_rsrc16(const void* base, int64_t nbytes) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)base);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((uintptr_t)base >> 32));
-    const unsigned nb = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(nbytes < 0xFFFFFFFFll ? (nbytes > 0 ? nbytes : 0) : 0xFFFFFFFFll));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | (uintptr_t)lo), 0, (int)nb, 0x00020000);
-}
-
 constexpr int PP_HT_B = 128 * HBK * 2;                   // one half-tile: 16 KB
 constexpr int PP_BUF_B = 4 * PP_HT_B;                    // [A0][A1][B0][B1] = 64 KB per k-tile
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -461,8 +451,7 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(const _Float16* __rest
                                                           const float* __restrict__ thr, uint8_t* __restrict__ gflag, int ngrp) {
     __shared__ __attribute__((aligned(1024))) char lds[2 * PP_BUF_B];       // the ONLY LDS object (a second one makes hipcc drain vmcnt before ds_reads)
     const int nwg = tiles_m * tiles_n;
-    const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, nwg);
     constexpr int GN = 8;
     const int per_group = GN * tiles_m, gid = wg / per_group, first_n = gid * GN;
     const int gsz = min(GN, tiles_n - first_n), within = wg - gid * per_group;
@@ -487,8 +476,8 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(const _Float16* __rest
     // buffer_load ... lds: a wave-uniform descriptor of the tile's 256 rows per operand, one constant 32-bit lane offset per
     // (half-tile, instruction), the k-tile offset as SGPR -- no vector address arithmetic in the load segments, where every
     // instruction beside the partner's MFMA stream is expensive.  Rows past the edge fall outside the descriptor (zeros, never stored).
-    const auto rq = uniform_rsrc16(Q + m0 * D, ((M - m0) < GBM ? (M - m0) : GBM) * (int64_t)D * 2);
-    const auto rg = uniform_rsrc16(G + n0 * D, ((N - n0) < GBN ? (N - n0) : GBN) * (int64_t)D * 2);
+    const auto rq = uniform_rsrc(Q + m0 * D, ((M - m0) < GBM ? (M - m0) : GBM) * (int64_t)D * 2);
+    const auto rg = uniform_rsrc(G + n0 * D, ((N - n0) < GBN ? (N - n0) : GBN) * (int64_t)D * 2);
     unsigned gvo[4][2];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -868,9 +857,9 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 }
 
 static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
+constexpr int kFastKlPct = 200;                     // candidates kept per query, in % of k (+ 32)
 static int fast_kl(int k) {
-    static const int pct = [] { const char* e = getenv("ISX_FAST_KL_PCT"); return e ? atoi(e) : 200; }();      // A/B: candidates kept per query, in % of k (+ 32)
-    int kl = (pct * k / 100 + 32 + 31) / 32 * 32;
+    int kl = (kFastKlPct * k / 100 + 32 + 31) / 32 * 32;
     if (kl < 64) kl = 64;
     if (kl > kGroupSelectMaxK) kl = kGroupSelectMaxK;
     return kl;

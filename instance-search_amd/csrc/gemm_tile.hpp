@@ -1,4 +1,4 @@
-// gemm_tile.hpp -- device helpers shared by the fp32-MFMA GEMM (cosine.hip) and the implicit-GEMM 3x3 convolution
+// gemm_tile.hpp -- device helpers shared by the fp32-MFMA GEMM (gemm.hip) and the implicit-GEMM 3x3 convolution
 // (conv.hip): XCD-aware tile mapping and the K-major LDS staging of operand tiles.
 #pragma once
 #include <type_traits>
@@ -18,9 +18,7 @@ struct TileMap {
 
 // b / nwg: block index and block count of the tile range (defaults: the whole grid)
 __device__ __forceinline__ void tile_of_block(const TileMap tm, int& tile_m, int& tile_n, int b, int nwg) {
-    // bijective XCD remap (blocks b and b+8 share an XCD): XCD x gets a contiguous id range
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+    const int wg = xcd_remap(b, nwg);
     // grouped order: GROUP_N n-tiles wide, all m-tiles tall, n fastest inside a group row
     const int per_group = GROUP_N * tm.tiles_m;
     const int gid = wg / per_group;
@@ -33,16 +31,6 @@ __device__ __forceinline__ void tile_of_block(const TileMap tm, int& tile_m, int
 
 __device__ __forceinline__ void tile_of_block(const TileMap tm, int& tile_m, int& tile_n) {
     tile_of_block(tm, tile_m, tile_n, (int)blockIdx.x, tm.tiles_m * tm.tiles_n);
-}
-
-// Raw buffer descriptor over [base, base + nbytes) from WAVE-UNIFORM inputs (readfirstlane makes that provable to hipcc: no waterfall
-// loops around the buffer instructions).  The two address halves go through unsigned temporaries: readfirstlane returns int, and
-// a sign-extended low half would corrupt the high half of the pointer.
-__device__ __forceinline__ auto uniform_rsrc(const void* base, int64_t nbytes) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)base);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((uintptr_t)base >> 32));
-    const unsigned nb = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(nbytes < 0xFFFFFFFFll ? (nbytes > 0 ? nbytes : 0) : 0xFFFFFFFFll));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | (uintptr_t)lo), 0, (int)nb, 0x00020000);
 }
 
 // ROWS x BK k = ROWS*CH float4; thread t takes idx = j*256 + t: row = idx/CH, chunk = idx%CH.

@@ -47,8 +47,7 @@ __global__ __launch_bounds__(256, TM * TN >= 6 ? 2 : TM * TN >= 3 ? 3 : 4) void 
     // row tiles fastest, and XCD x gets a contiguous range of tile ids (blocks b and b + 8 share an XCD): the row tiles that read the same slice of
     // the weight run next to each other on ONE XCD and share it in that L2
     const int nwg = (int)gridDim.x, bx = (int)blockIdx.x;
-    const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
+    const int wg = xcd_remap(bx, nwg);
     const int tile_m = wg % tiles_m, tile_n = wg / tiles_m, split = (int)blockIdx.y;
     const int m0 = tile_m * BM;
     const int64_t n0 = (int64_t)tile_n * BN;

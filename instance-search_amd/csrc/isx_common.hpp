@@ -107,6 +107,22 @@ __device__ __forceinline__ void bitonic_sort_desc(uint64_t* keys, int n) {
     __syncthreads();
 }
 
+// Bijective XCD remap: block b of nwg -> an id such that XCD x (blocks b and b + 8 share an XCD) gets a contiguous range of ids.
+__device__ __forceinline__ int xcd_remap(int b, int nwg) {
+    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+}
+
+// Raw buffer descriptor over [base, base + nbytes) from WAVE-UNIFORM inputs (readfirstlane makes that provable to hipcc: no waterfall
+// loops around the buffer instructions).  The two address halves go through unsigned temporaries: readfirstlane returns int, and
+// a sign-extended low half would corrupt the high half of the pointer.
+__device__ __forceinline__ auto uniform_rsrc(const void* base, int64_t nbytes) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)base);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((uintptr_t)base >> 32));
+    const unsigned nb = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(nbytes < 0xFFFFFFFFll ? (nbytes > 0 ? nbytes : 0) : 0xFFFFFFFFll));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | (uintptr_t)lo), 0, (int)nb, 0x00020000);
+}
+
 inline int next_pow2(int v) {
     int p = 1;
     while (p < v) p <<= 1;

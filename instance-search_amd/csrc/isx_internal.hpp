@@ -6,6 +6,21 @@
 
 namespace isx {
 
+// ---- the fp32 GEMM of gemm.hip ----------------------------------------------------------------------------------------------------
+// Epilogue modes (the EPI template argument of cosine_gemm_kernel) and the arguments of each mode.
+constexpr int kEpiScores = 0, kEpiFilter = 1, kEpiConv = 2, kEpiMaskedGrad = 3;
+template <int EPI> struct EpiArgs {};                                                     // kEpiScores: store every score
+// kEpiFilter: a 32-column group of row m is stored only if one of its scores reaches thr[m]; gflag (M x ngrp, ngrp = ceil(N/32)) flags them
+template <> struct EpiArgs<kEpiFilter> { const float* thr; uint8_t* gflag; int ngrp; };
+// kEpiConv: y = acc + bias[n] (+ residual, layout of C, or null), then max(y, 0) if relu
+template <> struct EpiArgs<kEpiConv> { const float* bias; const float* residual; int relu; };
+// kEpiMaskedGrad: C = (acc (+ add)) . [mask > 0]; mask and add have the layout of C, either may be null
+template <> struct EpiArgs<kEpiMaskedGrad> { const float* mask; const float* add; };
+using ScoresArgs = EpiArgs<kEpiScores>;
+using FilterArgs = EpiArgs<kEpiFilter>;
+using ConvArgs = EpiArgs<kEpiConv>;
+using MaskedGradArgs = EpiArgs<kEpiMaskedGrad>;
+
 // C[m][n] = sum_k Q[m][k] * G[n][k]  (k-ordered fp32 fma chain), C row stride ldc.
 // m_active (optional, device scalar): tiles whose first row is >= *m_active exit immediately.
 int launch_cosine_gemm(const float* Q, int64_t M, const float* G, int64_t N, int D, float* C, int64_t ldc,
@@ -21,12 +36,15 @@ int launch_cosine_gemm_filter(const float* Q, int64_t M, const float* G, int64_t
 int launch_conv1x1_gemm(const float* x, int64_t M, const float* w, int64_t N, int D, float* y, const float* bias, const float* residual, int relu,
                         hipStream_t st);
 
+// Gradient of a 1x1 convolution wrt its input (backward.hip): C = (A . Bt^T (+ add)) . [mask > 0], C row stride N
+int launch_gemm_masked(const float* A, int64_t M, const float* Bt, int64_t N, int D, float* C, const float* mask, const float* add, hipStream_t st);
+
 // Tail of a convolution launch in 128x128 tiles: rows covered by whole rounds of 1024 resident workgroups when the rest of the grid is a
 // partial round -- the caller runs the remaining rows as 64x64 tiles in the same grid; 0 = no split.  g_tail_split: debug / A-B switch.
 extern std::atomic<int> g_tail_split;      // (the debug / A-B knobs are relaxed atomics: a test thread may flip them while another thread launches)
 int64_t gemm_tail_split_rows(int64_t M, int64_t N, int64_t slots = 1024);       // slots: resident 128x128 workgroups of the calling kernel (256 CUs x workgroups per CU)
 // Tile shape (0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64) with the smallest estimated launch time among those in `mask` (rounds of resident
-// workgroups + tail + per-CU quantisation, cosine.hip); eff[4]: steady-state efficiency per shape of the calling kernel family.
+// workgroups + tail + per-CU quantisation, gemm.hip); eff[4]: steady-state efficiency per shape of the calling kernel family.
 int pick_tile_cfg(int64_t M, int64_t N, int64_t split, const float* eff, unsigned mask, int wg_per_cu_128 = 4);
 
 // Streaming variant for the HBM-bound Cin = 64 layers (stream1x1.hip): persistent workgroups, weights in registers, pixel tiles by LDS-DMA.
@@ -34,7 +52,7 @@ bool conv1x1_stream_applicable(int64_t M, int Cin, int Cout, const float* x, con
 int launch_conv1x1_stream(const float* x, int64_t M, const float* w, int Cin, int Cout, const float* bias, const float* res, int relu, float* y,
                           hipStream_t st);
 
-// fp16-operand variant (fast.hip): approximate scores, fp32 accumulate; gflag == nullptr -> plain GEMM.
+// fp16-operand variant (fast.hip): approximate scores, fp32 accumulate; the kEpiFilter epilogue, gflag == nullptr -> plain GEMM.
 int launch_gemm_f16(const _Float16* Q, int64_t M, const _Float16* G, int64_t N, int D, float* C, int64_t ldc, const float* thr,
                     uint8_t* gflag, hipStream_t st);
 

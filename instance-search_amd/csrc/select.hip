@@ -113,7 +113,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// Running top-k update from a chunk produced by the FILTERING GEMM epilogue (cosine.hip, fast.hip): one
+// Running top-k update from a chunk produced by the FILTERING GEMM epilogue (gemm.hip, fast.hip): one
 // wave (64-thread workgroup) per query row.  gflag marks the 32-column groups the GEMM stored (those
 // with a score reaching the row's threshold); nothing else can change the list.  The wave scans the
 // flag row 64 groups at a time, then reads up to eight qualifying 128-B segments per step (four

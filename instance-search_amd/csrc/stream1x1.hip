@@ -1,5 +1,5 @@
 // stream1x1.hip -- the Cin = 64 1x1 convolutions of the first ResNet stage at 56x56 (64->64, 64->256 + residual), written as a
-// STREAMING kernel.  These layers move 0.5-2.3 KB per pixel for 8-33 kFLOP: they are HBM-bound, and the tiled GEMM of cosine.hip
+// STREAMING kernel.  These layers move 0.5-2.3 KB per pixel for 8-33 kFLOP: they are HBM-bound, and the tiled GEMM of gemm.hip
 // (isx_conv1x1_nhwc's general path) holds them at ~4.0 TB/s because a tile's loads, MFMAs and stores follow each other inside
 // a workgroup and only other workgroups overlap them.  Here one persistent 512-thread workgroup per CU walks the pixel tiles:
 //   * the weights live in REGISTERS for the whole kernel (wave w owns 32 output channels: 32 VGPRs = the B operands of the 32
