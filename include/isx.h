@@ -359,6 +359,33 @@ int isx_triplet_loss_bwd_dev(const float* anchor, const float* pos, const float*
 int isx_triplet_leaves(const float* d, int leaves, int k, int D, float margin, int normalized, float scale_a, float scale_b, float* loss_leaf,
                        float* dd, isx_stream_t stream);
 
+/* ---- classification fine-tuning (pipeline stage 1, csrc/classif.hip) ----
+ * Softmax cross-entropy: nn.CrossEntropyLoss of train/classif_finetune.py:154, called once per micro-batch from
+ * utils/train_general.py:51-61.  logits: (B, C) fp32; labels: (B) int32 in [0, C) (an out-of-range label gives a NaN loss and no out-of-bounds
+ * read; train.classif_finetune.train_classif checks its label list on the host, the ops wrappers do not).  One wave per row: m = max_j z_j; s = sum_j exp(z_j - m), lane i adding its columns i, i + 64, ... in ascending
+ * order from +0, the 64 lane sums meeting in a butterfly (xor 32, 16, 8, 4, 2, 1); loss_rows[b] = log s + m - z_label (before any sum / mean).
+ * A row's values do not depend on the rows around it. */
+int isx_softmax_xent_fwd(const float* logits, const int32_t* labels, int64_t B, int C, float* loss_rows, isx_stream_t stream);
+/* dlogits[b][j] = (exp(z_j - m) / s - [j == label_b]) * scale * scale_dev[0]; scale_dev: autograd's grad_output left on the device (as
+ * isx_triplet_loss_bwd_dev), or NULL for 1. */
+int isx_softmax_xent_bwd(const float* logits, const int32_t* labels, int64_t B, int C, float scale, const float* scale_dev, float* dlogits,
+                         isx_stream_t stream);
+/* The same loss and gradient for ALL micro-batches ("leaves") of an optimizer step in ONE launch.  logits: (leaves * k, C), labels: (leaves * k).
+ * loss_leaf[l] = the leaf's row losses added in row order (before any averaging); dlogits rows as isx_softmax_xent_bwd forms them with
+ * scale = scale_a * scale_b (1 / k when the loss is averaged, times the weight of the leaf in the mini-batch).  A leaf's loss and gradient are
+ * the same bits whether it is launched alone or with its siblings -- the contract of isx_triplet_leaves. */
+int isx_softmax_xent_leaves(const float* logits, const int32_t* labels, int leaves, int k, int C, float scale_a, float scale_b, float* loss_leaf,
+                            float* dlogits, isx_stream_t stream);
+
+/* Backward of the whole-map average pool in front of the classifier (model/siamese.py:20-23 AvgPool2d(7) on the 7 x 7 trunk output), WITHOUT
+ * the ReLU mask of the block below (isx_relu_grad follows): dx[b][h][w][c] = g[b][c] / (H * W).  g: (B, C); dx: (B,H,W,C); C % 4 == 0. */
+int isx_gap_bwd_nhwc(const float* g, int64_t B, int H, int W, int C, float* dx, isx_stream_t stream);
+
+/* Per-leaf weight gradient of the classifier Linear(2048 -> num_classes) (model/siamese.py:28-32; autograd forms it once per micro-batch,
+ * utils/train_general.py:51-61): dw[l][n][k] = sum_{r < R} dy[l R + r][n] * x[l R + r][k], ONE fp32 fma chain from +0 over the leaf's rows in
+ * row order, never split.  dy: (leaves * R, N), x: (leaves * R, K), dw: (leaves, N, K); any N, K % 4 == 0. */
+int isx_linear_wgrad_leaves(const float* dy, const float* x, int leaves, int R, int N, int K, float* dw, isx_stream_t stream);
+
 /* model/custom_modules.py:59-67 NormalizeL2Fun.backward: with n2 = sum_j x_j^2 + eps and c = sum_j x_j dy_j,
  * dx = (n2 dy - x c) / (n2 sqrt(n2)).  x, dy, dx: (B, D). */
 int isx_l2norm_rows_bwd(const float* x, const float* dy, int64_t B, int64_t D, float eps, float* dx, isx_stream_t stream);

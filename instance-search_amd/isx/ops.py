@@ -834,6 +834,74 @@ def triplet_leaves(d_all, leaves, margin, normalized=True, scale_a=1.0, scale_b=
     return loss, dd
 
 
+# ---- classification fine-tuning (csrc/classif.hip) ---------------------------------------------------
+def _xent_args(logits, labels):
+    logits = _f32(logits, "logits")
+    if logits.dim() != 2 or labels.dim() != 1 or labels.numel() != logits.size(0):
+        raise _lib.IsxError("softmax cross-entropy: logits (B, C) and labels (B), got %s and %s" % (tuple(logits.shape), tuple(labels.shape)))
+    return logits, _typed(labels, torch.int32, "labels")
+
+
+def softmax_xent_rows(logits, labels):
+    """Per-row cross-entropy log sum_j exp(z_j) - z_label (isx_softmax_xent_fwd).  Labels must lie in [0, C): the caller's contract -- this wrapper does not
+    read the labels back to check them (train.classif_finetune.train_classif checks its label list on the host before the first step); an
+    out-of-range label yields a NaN loss and reads nothing out of bounds."""
+    logits, labels = _xent_args(logits, labels)
+    B, Cc = logits.shape
+    rows = torch.empty((B,), device=logits.device, dtype=torch.float32)
+    check(lib().isx_softmax_xent_fwd(logits.data_ptr(), labels.data_ptr(), B, Cc, rows.data_ptr(), _stream()), "isx_softmax_xent_fwd")
+    return rows
+
+
+def softmax_xent_grad(logits, labels, scale=1.0, scale_dev=None):
+    """(softmax(z) - onehot(label)) * scale [* scale_dev[0]]; scale_dev: optional 1-element float32 CUDA tensor (autograd's grad_output)."""
+    logits, labels = _xent_args(logits, labels)
+    B, Cc = logits.shape
+    dz = torch.empty_like(logits)
+    sd_ = _f32(scale_dev.reshape(-1), "scale_dev") if scale_dev is not None else None
+    check(lib().isx_softmax_xent_bwd(logits.data_ptr(), labels.data_ptr(), B, Cc, float(scale), sd_.data_ptr() if sd_ is not None else None,
+                                     dz.data_ptr(), _stream()), "isx_softmax_xent_bwd")
+    return dz
+
+
+def softmax_xent_leaves(logits, labels, leaves, scale_a=1.0, scale_b=1.0):
+    """Cross-entropy + gradient of every micro-batch of a step in one launch (isx_softmax_xent_leaves).  logits: (leaves * k, C).
+    Returns (per-leaf sum of the row losses (leaves,), gradient rows like logits scaled by scale_a * scale_b)."""
+    logits, labels = _xent_args(logits, labels)
+    R, Cc = logits.shape
+    if leaves <= 0 or R % leaves:
+        raise _lib.IsxError("softmax_xent_leaves: %d rows do not split into %d equal leaves" % (R, leaves))
+    loss = torch.empty((leaves,), device=logits.device, dtype=torch.float32)
+    dz = torch.empty_like(logits)
+    check(lib().isx_softmax_xent_leaves(logits.data_ptr(), labels.data_ptr(), leaves, R // leaves, Cc, float(scale_a), float(scale_b),
+                                        loss.data_ptr(), dz.data_ptr(), _stream()), "isx_softmax_xent_leaves")
+    return loss, dz
+
+
+def gap_bwd_nhwc(g, H, W):
+    """Backward of the whole-map average pool: g (B, C) -> channels-last (B, C, H, W) with every pixel g / (H W) (isx_gap_bwd_nhwc)."""
+    g = _f32(g, "g")
+    B, Cc = g.shape
+    dx = torch.empty((B, Cc, H, W), device=g.device, dtype=torch.float32, memory_format=torch.channels_last)
+    if B * H * W * Cc and (H * W == 1 or Cc == 1):           # degenerate strides: torch may not lay such a tensor out as (B,H,W,C)
+        dx = torch.empty((B, H, W, Cc), device=g.device, dtype=torch.float32).permute(0, 3, 1, 2)
+    check(lib().isx_gap_bwd_nhwc(g.data_ptr(), B, H, W, Cc, dx.data_ptr(), _stream()), "isx_gap_bwd_nhwc")
+    return dx
+
+
+def linear_wgrad_leaves(dy, x, leaves):
+    """dw[l] = dy_l^T x_l for `leaves` consecutive groups of rows, one row-ordered fp32 fma chain per element (isx_linear_wgrad_leaves).
+    dy: (leaves * R, N), x: (leaves * R, K) -> (leaves, N, K)."""
+    dy, x = _f32(dy, "dy"), _f32(x, "x")
+    M, N = dy.shape
+    if x.dim() != 2 or x.size(0) != M or leaves <= 0 or M % leaves:
+        raise _lib.IsxError("linear_wgrad_leaves: dy %s and x %s do not split into %d equal leaves" % (tuple(dy.shape), tuple(x.shape), leaves))
+    K = x.size(1)
+    dw = torch.empty((leaves, N, K), device=dy.device, dtype=torch.float32)
+    check(lib().isx_linear_wgrad_leaves(dy.data_ptr(), x.data_ptr(), leaves, M // leaves, N, K, dw.data_ptr(), _stream()), "isx_linear_wgrad_leaves")
+    return dw
+
+
 # ---- half-precision filter path (csrc/fast.hip) ----------------------------------------------------
 def rows_to_f16(x):
     """(h (B,D) float16, norm2 (B) upper bound of the squared row norm, amax (B) max |x|)."""

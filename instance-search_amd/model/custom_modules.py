@@ -215,6 +215,44 @@ class TripletLoss(nn.Module):
         return _Triplet.apply(anchor, pos, neg, self.margin, self.size_average, self.normalized)
 
 
+class _CrossEntropy(Function):
+    """Softmax cross-entropy of fp32 GPU logits on libisx (isx_softmax_xent_fwd / _bwd): per-row losses in a fixed summation order, their sum
+    (or mean) formed by torch, the gradient from the logits alone with autograd's grad_output read on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, size_average):
+        from isx import ops
+        z = logits.detach()
+        lab = target.to(torch.int32)
+        rows = ops.softmax_xent_rows(z, lab)
+        ctx.save_for_backward(z, lab)
+        ctx.size_average = size_average
+        loss = rows.sum()
+        return loss / z.size(0) if size_average else loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from isx import ops
+        z, lab = ctx.saved_tensors
+        scale = 1.0 / z.size(0) if ctx.size_average else 1.0
+        return ops.softmax_xent_grad(z, lab, scale, scale_dev=grad_output.detach().float().to(z.device)), None, None
+
+
+class CrossEntropyLoss(nn.Module):
+    """nn.CrossEntropyLoss(size_average=...) as the reference builds it (train/classif_finetune.py:154): input (B, C) class scores, target (B)
+    class indices; a scalar, the mean over the batch (size_average) or the sum.  fp32 GPU scores run on libisx; CPU tensors (and other
+    dtypes) are torch's F.cross_entropy, bit for bit."""
+
+    def __init__(self, size_average=True):
+        super().__init__()
+        self.size_average = size_average
+
+    def forward(self, input, target):
+        if input.is_cuda and input.dtype == torch.float32 and input.dim() == 2:
+            return _CrossEntropy.apply(input, target, self.size_average)
+        return nn.functional.cross_entropy(input, target, reduction='mean' if self.size_average else 'sum')
+
+
 class MetricLossFun(object):
     """Chopra et al. contrastive loss with Q = 2 on the L1 energy E = |x1 - x2|_1:
     (1+y)/2 * E^2 + (1-y) * 2 * exp(-2.77 E / 2), y = +1 (same) / -1 (different).  Plain torch autograd."""

@@ -104,9 +104,76 @@ class TuneClassif(nn.Module):
         _box_pools(self.feature_reduc)
 
     def forward(self, x):
-        x = self.features(x)
+        if self.training and torch.is_grad_enabled() and x.is_cuda:
+            x = self._split_trunk()(self.features, x)          # fine-tuning on the GPU: frozen prefix on the folded HIP trunk (_SplitTrunk)
+        else:
+            x = self.features(x)
         x = self.feature_reduc(x)
         return self.classifier(x.reshape(x.size(0), -1))     # logical (C,h,w) order whatever the memory format
+
+    # ---- hooks of the training step (utils/train_general._Stepper), one branch: what DescriptorNet offers for its three ------------------
+    def _split_trunk(self):
+        t = self.__dict__.get('_trunk')
+        if t is None:
+            t = self.__dict__['_trunk'] = _SplitTrunk()
+        return t
+
+    def trunk_precomputable(self):
+        """True when precompute_trunk can serve training steps: training mode, GPU, a frozen trunk prefix, BatchNorm not learning."""
+        p = next(self.features.parameters(), None)
+        return bool(self.training and p is not None and p.is_cuda and _SplitTrunk.enabled(self.features))
+
+    def precompute_trunk(self, x, cache=False):
+        """The frozen trunk prefix of a whole image batch in one launch of the folded inference trunk (see DescriptorNet.precompute_trunk);
+        None when the trunk has to run inside the step (nothing frozen, BatchNorm learning, CPU tensors, eval mode)."""
+        trunk = self._split_trunk()
+        if not self.training or not (x.is_cuda and x.dtype == torch.float32) or not trunk.usable(self.features, x):
+            return None
+        if cache:
+            got = trunk.prefix_cached(self.features, (x,))
+            if got is not None:
+                return got
+        f, _ = trunk.prefix(self.features, x)
+        return (f,)
+
+    def suffix_engine(self):
+        """The libisx engine of the trainable trunk suffix when a training step may drive it directly, else None (DescriptorNet.suffix_engine)."""
+        trunk = self._split_trunk()
+        if not (self.trunk_precomputable() and SUFFIX_ENGINE and trunk.folded is not None):
+            return None
+        mods = list(self.features)[trunk.split:]
+        if not mods or not any(p.requires_grad for m in mods for p in m.parameters()):
+            return None
+        from isx.suffix import SuffixEngine
+        eng = _SplitTrunk._engine_of(self.features, trunk.split, mods)
+        return eng if eng and SuffixEngine.applicable(mods) else None
+
+    def classif_head_engine(self):
+        """The libisx engine of pool -> Linear -> cross-entropy for all local micro-batches of a training step at once (isx/classif_head.py), when
+        the step may drive it by hand: a single Linear behind a whole-map average pool (the ResNets), GPU training with a precomputable trunk
+        whose trainable part (if any) runs on the suffix engine.  ISX_CLASSIF_ENGINE=0: None (the tail stays on torch autograd)."""
+        trunk = self._split_trunk()
+        if not (CLASSIF_ENGINE and self.trunk_precomputable() and trunk.folded is not None):
+            return None
+        mods = list(self.features)[trunk.split:]
+        if any(p.requires_grad for m in mods for p in m.parameters()) and self.suffix_engine() is None:
+            return None
+        from isx.classif_head import ClassifHeadEngine
+        if not ClassifHeadEngine.applicable(self):
+            return None
+        eng = self.__dict__.get("_classif_head_engine")
+        if eng is None or eng.lin is not self.classifier[0] or eng.pool is not self.feature_reduc[0]:
+            eng = self.__dict__["_classif_head_engine"] = ClassifHeadEngine(self)
+        return eng
+
+    def head_rows(self, f, n_branches=1):
+        """pool + classifier on the trunk output of one branch (torch autograd when f carries a graph): the class scores"""
+        f = self.feature_reduc(f)
+        return self.classifier(f.reshape(f.size(0), -1))
+
+    def forward_features(self, f):
+        """forward() of training mode on precomputed prefix features: trainable suffix + pool + classifier"""
+        return self.head_rows(_SplitTrunk.suffix(self.features, f, self._split_trunk().split))
 
 
 class TuneClassifSub(TuneClassif):
@@ -120,6 +187,9 @@ class TuneClassifSub(TuneClassif):
     def forward_single(self, x):
         return self.classifier(self.feature_reduc(self.features(x)))
 
+    def trunk_precomputable(self):
+        return False                                         # multi-scale score maps: none of TuneClassif's one-branch training hooks apply
+
     def forward(self, *scales):
         return [self.forward_single(x) for x in scales]
 
@@ -131,6 +201,8 @@ SPLIT_TRUNK = os.environ.get("ISX_SPLIT_TRUNK", "1") != "0"
 SUFFIX_ENGINE = os.environ.get("ISX_SUFFIX_ENGINE", "1") != "0"
 # A/B switch: ISX_HEAD_ENGINE=0 keeps the descriptor head of a training step on torch autograd, micro-batch by micro-batch.
 HEAD_ENGINE = os.environ.get("ISX_HEAD_ENGINE", "1") != "0"
+# A/B switch: ISX_CLASSIF_ENGINE=0 keeps pool + classifier + cross-entropy of a classification fine-tuning step on torch autograd, micro-batch by micro-batch.
+CLASSIF_ENGINE = os.environ.get("ISX_CLASSIF_ENGINE", "1") != "0"
 PREFIX_CACHE_BUDGET = int(os.environ.get("ISX_PREFIX_CACHE_GB", "96")) << 30      # HBM the prefix-feature cache of ONE resident set may take
 
 

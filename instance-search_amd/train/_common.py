@@ -448,14 +448,14 @@ def load_training_sets(P, dataset_full, labels):
 
 def training_cli(argv, P, run, what):
     """`python -m train.<approach> --dataset=<folder | synthetic:...> [--model=] [--device=] [--epochs=] [--classif-model=] [--preload-net=]
-    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=]`: the reference's training scripts take everything from their
+    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=]`: the reference's training scripts take everything from their
     *_p.py file (edit and run); the same fields can be given here instead."""
     import getopt
     import sys
     spec = {'dataset': ('dataset_full', str), 'model': ('cnn_model', str), 'device': ('cuda_device', int), 'epochs': ('train_epochs', int),
             'classif-model': ('classif_model', str), 'preload-net': ('preload_net', str), 'save-dir': ('save_dir', str),
             'feature-dim': ('feature_dim', int), 'batch-size': ('train_batch_size', int), 'micro-batch': ('train_micro_batch', int),
-            'lr': ('train_lr', float), 'seed': ('train_seed', int)}
+            'lr': ('train_lr', float), 'seed': ('train_seed', int), 'loss-int': ('train_loss_int', int)}
     try:
         opts, _ = getopt.getopt(argv, '', ['help'] + [k + '=' for k in spec])
     except getopt.GetoptError as e:

@@ -1,13 +1,18 @@
-"""Global-descriptor approach: the retrieval-path functions of the reference's
-train/classif_finetune.py -- get_embeddings (:82-110), get_class_net (:113-121),
-test_classif_net (:25-50).  The fine-tuning loop (:53-78, main) is out of scope."""
+"""Global-descriptor approach, pipeline stage 1: the reference's train/classif_finetune.py -- get_embeddings (:82-110), get_class_net
+(:113-121), test_classif_net (:25-50) and the fine-tuning of the backbone as a classifier on the instance labels (train_classif :53-78,
+main :124-167), whose checkpoint the siamese trainings start from (P.classif_model).  On the GPU the frozen trunk prefix runs once per
+mini-batch on the folded HIP trunk, layer4 on isx.suffix.SuffixEngine and pool -> classifier -> cross-entropy on isx.classif_head
+(utils/train_general._Stepper); on the CPU, with BatchNorm learning or for AlexNet's classifier the step is plain torch autograd."""
+import random
+
 import torch
 import torch.nn as nn
 
-from model.custom_modules import l2_normalize_rows
+from model.custom_modules import CrossEntropyLoss, l2_normalize_rows
 from model.siamese import TuneClassif
-from utils import fold_batches, move_device, tensor
-from ._common import BatchStager, base_model, device_batch_size, label_index, load_weights, make_resident, stage_batch, test_transform
+from utils import fold_batches, log, move_device, tensor, test_print_classif, test_print_descriptor, train_gen
+from ._common import (BatchStager, base_model, device_batch_size, label_index, load_weights, make_resident, stage_batch, stage_images,
+                      test_transform)
 from .classif_finetune_p import P
 
 labels = []   # filled by the entry point once the reference set is listed, then constant
@@ -98,3 +103,87 @@ def get_embeddings(net, dataset, device, out_size):
 def get_class_net():
     net = TuneClassif(base_model(P), len(labels), untrained=P.untrained_blocks)
     return move_device(load_weights(net, P.preload_net), P.cuda_device)
+
+
+def train_classif(net, train_set, testset_tuple, criterion, optimizer, best_score=0):
+    """Fine-tune `net` as a classifier of the instance labels (reference :53-78): per epoch the training set is shuffled, a batch is the image
+    rows + the label indices, the loss is `criterion` on the class scores."""
+    trans = None if P.train_pre_proc else P.train_trans
+    if trans is None:
+        make_resident(train_set, P.cuda_device)          # batches become row gathers on the device
+    ids = label_index(labels)
+    unknown = sorted(set(lab for _, lab, _ in train_set if lab not in ids))
+    if unknown:
+        raise ValueError('train_classif: %d training labels are not in the label list (first: %r)' % (len(unknown), unknown[0]))
+    if len(labels) > net.feature_size:
+        raise ValueError('train_classif: %d labels but the net scores %d classes' % (len(labels), net.feature_size))
+
+    def create_epoch(epoch, train_set, testset_tuple):
+        shuffled = list(train_set)                       # the caller's list keeps its order (it may double as the evaluation gallery)
+        random.shuffle(shuffled)
+        return shuffled, {}
+
+    def create_batch(batch, n):
+        prep = (lambda im: im) if trans is None else trans
+        x = stage_images([prep(im) for im, _, _ in batch], P.cuda_device)
+        ids = label_index(labels)
+        lab_ids = torch.tensor([ids[lab] for _, lab, _ in batch], dtype=torch.int64)
+        return [x], [move_device(lab_ids, P.cuda_device)]
+
+    # same items -> same batch, whenever it is built (nothing is augmented): the step may build the batches of the next mini-batches ahead of
+    # their turn (utils/train_general._Stepper._precompute_ahead)
+    create_batch.deterministic = trans is None
+
+    def create_loss(t_out, labels_list):
+        return criterion(t_out, labels_list[0]), None
+
+    # the loss IS the cross-entropy criterion on the class scores: the step may evaluate pool, classifier and loss of all its micro-batches in
+    # one pass (utils/train_general._Stepper._leaves_batched -> isx.classif_head), same values per row
+    if type(criterion) is CrossEntropyLoss:
+        create_loss.cross_entropy = criterion
+
+    return train_gen(train_type(), P, test_print_classif, test_classif_net, net, train_set, testset_tuple, optimizer, create_epoch,
+                     create_batch, create_loss, best_score=best_score)
+
+
+def train_type():
+    return P.cnn_model.lower() + ' Classification simple fine-tuning'
+
+
+def main(train_set, test_train_set, test_set):
+    """Training entry (reference :124-167) on already loaded (tensor, label, path) datasets: upfront test (P.test_upfront) -> training
+    (P.train) -> evaluation as a descriptor net (P.test_descriptor_net).  Returns (net, best classification score)."""
+    from utils.train_general import make_sgd
+    from .global_p import flat_feature_sizes
+    del labels[:]
+    labels.extend(sorted(set(l for _, l, _ in train_set)))
+    P.num_classes = len(labels)
+    net = get_class_net()
+    optimizer = make_sgd((p for p in net.parameters() if p.requires_grad), P.train_lr, P.train_momentum, P.train_weight_decay)
+    criterion = CrossEntropyLoss(size_average=P.train_loss_avg)
+    testset_tuple = (test_set, test_train_set)
+    score = 0
+    if getattr(P, 'test_upfront', True):
+        log(P, 'Upfront testing of classification model')
+        score = test_print_classif(train_type(), P, net, testset_tuple, test_classif_net)
+    if getattr(P, 'train', True):
+        log(P, 'Starting classification training')
+        score = train_classif(net, train_set, testset_tuple, criterion, optimizer, best_score=score)
+        log(P, 'Finished classification training')
+    if getattr(P, 'test_descriptor_net', True):
+        log(P, 'Testing as descriptor')
+        P.feature_dim = P.num_classes if P.embeddings_classify else flat_feature_sizes.get((P.cnn_model.lower(), tuple(P.image_input_size)), P.feature_dim)
+        test_print_descriptor(train_type(), P, net, testset_tuple, get_embeddings)
+    return net, score
+
+
+def run(dataset_full=None):
+    """The reference's main() (:124-167): the sets come from P.dataset_full (a dataset folder with its `test` sub-folder, or a `synthetic:` spec)."""
+    from ._common import load_training_sets
+    return main(*load_training_sets(P, dataset_full or P.dataset_full, labels))
+
+
+if __name__ == '__main__':
+    import sys
+    from ._common import training_cli
+    training_cli(sys.argv[1:], P, run, 'train.classif_finetune')

@@ -5,3 +5,4 @@ from .dataset import *          # noqa: F401,F403
 from .metrics import *          # noqa: F401,F403
 from .train_general import *    # noqa: F401,F403
 from .train_siamese import *    # noqa: F401,F403
+from .train_classif import *    # noqa: F401,F403

@@ -169,13 +169,14 @@ class _Stepper(object):
             return None
         return feats, targets
 
-    def _leaves_batched(self, eng, head, mine, offsets, mini_size, pre, sink):
+    def _leaves_batched(self, eng, head, mine, offsets, mini_size, pre, sink, chead=None):
         """All local micro-batches through the trainable trunk suffix (isx/suffix.py) and -- when `head` is given -- the descriptor head
         (isx/head.py) in ONE forward and ONE backward each, their gradients kept apart per micro-batch.  Every row is computed exactly as in
         a launch of its own, per-leaf sums run over the leaf's rows / pixels in order: each leaf's flat gradient is bit for bit what a pass
         over that leaf alone produces -- and what a rank of a P-rank run computes.  The loss is the training script's own callback,
         evaluated per micro-batch on its rows.  Without `head` the head runs micro-batch by micro-batch under torch autograd on its rows of
-        the suffix output.  Returns (flat_all (L, total), losses)."""
+        the suffix output.  `chead` (classification fine-tuning, isx/classif_head.py): pool, classifier and cross-entropy of all leaves in one
+        pass instead.  Returns (flat_all (L, total), losses)."""
         P = self.P
         feats, targets_all = pre
         nb, k, L = len(feats), len(mine[0]), len(mine)
@@ -203,6 +204,25 @@ class _Stepper(object):
 
         ph = _phase("heads")
         ph.__enter__()
+        if chead is not None:
+            # classification fine-tuning: the training script declared its loss to be THE cross-entropy criterion on the class scores of the
+            # net's one branch (`create_loss.cross_entropy = criterion`): pool, classifier, loss and their backward for all L micro-batches in
+            # one pass (isx/classif_head.py), the leaf's loss = its rows' losses in row order
+            xent = self.make_loss.cross_entropy
+            labels = torch.cat([targets_all[0][o:o + k] for o in offsets], 0)
+            share = k / float(mini_size)
+            per_leaf, dy_all = chead.step(y_all, labels, L, (1.0 / k) if xent.size_average else 1.0, share if P.train_loss_avg else 1.0,
+                                          flat_all, self.flat.slices, need_dy=eng is not None)
+            if xent.size_average:
+                per_leaf = per_leaf / k
+            if P.train_loss_avg:
+                per_leaf = per_leaf * share
+            losses.extend(per_leaf.unbind(0))
+            ph.__exit__()
+            if eng is not None:
+                with _phase("suffix_backward"):
+                    eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
+            return flat_all, losses
         if head is not None:
             from model.siamese import _SplitRows
             shard = sink.shard_for(head.lin.weight) if sink is not None else None
@@ -336,20 +356,22 @@ class _Stepper(object):
             for sh in sink.shards.values():
                 sh.begin_step(len(mine))
             sink.leaf_ids = list(range(lo, hi))
-            eng = head = None
+            eng = head = chead = None
             batched = getattr(self.P, 'train_suffix_batched', True)
             # batched engines need equal micro-batches; decided from the MINI-BATCH (n % mb == 0: every leaf of every rank has mb triplets), not from
             # this rank's leaves, so that every rank and the single-process run take the same numeric path (round-4 ADVICE)
             if self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched:
                 eng = getattr(self.net, 'suffix_engine', lambda: None)()
                 head = getattr(self.net, 'head_engine', lambda: None)()
-            if eng is not None or head is not None:
+                if getattr(self.make_loss, 'cross_entropy', None) is not None:
+                    chead = getattr(self.net, 'classif_head_engine', lambda: None)()     # classification fine-tuning (TuneClassif), else None
+            if eng is not None or head is not None or chead is not None:
                 if batched == "leaf":                # test mode: the same machinery one micro-batch at a time (what a rank with ONE leaf runs)
-                    parts = [self._leaves_batched(eng, head, [mine[j]], [offsets[j]], n, pre, sink) for j in range(len(mine))]
+                    parts = [self._leaves_batched(eng, head, [mine[j]], [offsets[j]], n, pre, sink, chead) for j in range(len(mine))]
                     flat_all = torch.cat([p[0] for p in parts], 0)
                     losses = [l for p in parts for l in p[1]]
                 else:
-                    flat_all, losses = self._leaves_batched(eng, head, mine, offsets, n, pre, sink)
+                    flat_all, losses = self._leaves_batched(eng, head, mine, offsets, n, pre, sink, chead)
                 if flat_all.is_cuda and 1 <= hi - lo <= 16:
                     from isx import ops
                     self.flat.attach_all()
