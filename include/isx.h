@@ -445,7 +445,12 @@ int isx_bn_fold_backward(const float* dwp, const float* db, int leaves, int spli
 /* y = x . w^T + bias with every row's value independent of how many rows ride along: S = isx_head_linear_splits(K) partial sums per
  * output (k-ordered fp32 fma chains over consecutive K ranges), added in split order.  xT: (K, Mp) = x TRANSPOSED, Mp >= M a multiple
  * of 64 (padding columns: any finite values); w: (N, K) as nn.Linear stores it; bias: (N) or NULL; y: (M, N); ws: S * Mp * N floats.
- * K % 32 == 0, N % 64 == 0. */
+ * K % 32 == 0, N % 64 == 0.
+ * The split rule, a function of K alone (pinned bit for bit by tests/test_gpu_head_chains.py): S = clamp(K / 2048, 1, 32) (integer division);
+ * the K / 32 k-tiles of 32 are dealt out kt_per = ceil((K / 32) / S) to a split: split s owns the k-tiles [s * kt_per, (s + 1) * kt_per),
+ * i.e. k in [32 s kt_per, min(K, 32 (s + 1) kt_per)) -- the last split takes what is left.  p_s = the fma chain over the k of split s in
+ * ascending k, from +0;  y = (((p_0 + p_1) + p_2) + ... + p_{S-1}), partials added from split 0 upward, THEN + bias[n]: one fp32 rounding
+ * per add.  Whatever M, Mp and the tile shape a launch picks. */
 int isx_head_linear_splits(int64_t K);
 int isx_head_linear_fwd(const float* xT, int64_t M, int64_t Mp, int64_t K, const float* w, int N, const float* bias, float* y,
                         float* ws, size_t ws_bytes, isx_stream_t stream);
@@ -472,7 +477,14 @@ int isx_head_linear_dgrad_parts(const float* dyT, int64_t Mp, int Ng, int groups
  * model/siamese.py:104-114): g[n][k] = sum_r dy[r][n] x[r][k] (one fp32 fma chain over the rows in row order), then per element
  *   g += weight_decay * w;  buf = first ? g : momentum * buf + (1 - dampening) * g;  w -= lr * (nesterov ? g + momentum * buf : buf)
  * dy: (R, N), x: (R, K), w / mom: (N, K) updated in place (mom NULL when momentum == 0).  N % 64 == 0, K % 128 == 0.  No dW tensor:
- * 4 passes over the weight's size per step instead of 7. */
+ * 4 passes over the weight's size per step instead of 7.
+ * The update is UNFUSED fp32 arithmetic, one rounding per multiply and per add (no fma contraction), in the order shown:
+ *   g = g + weight_decay * w            (only when weight_decay != 0)
+ *   buf = g on the first step, else momentum * buf + (1 - dampening) * g, 1 - dampening formed in fp32   (only when momentum != 0; the
+ *   first step does not read mom)
+ *   upd = nesterov ? g + momentum * buf : buf;  without momentum upd = g
+ *   w = w - lr * upd
+ * so a CPU that performs these fp32 operations one by one on the same chain g lands on the same bits (tests/_head_model.py sgd_step). */
 int isx_head_sgd_step(const float* dy, const float* x, int64_t R, int N, int64_t K, float* w, float* mom, int first, float lr,
                       float momentum, float dampening, float weight_decay, int nesterov, isx_stream_t stream);
 
