@@ -381,6 +381,14 @@ int isx_softmax_xent_leaves(const float* logits, const int32_t* labels, int leav
  * the ReLU mask of the block below (isx_relu_grad follows): dx[b][h][w][c] = g[b][c] / (H * W).  g: (B, C); dx: (B,H,W,C); C % 4 == 0. */
 int isx_gap_bwd_nhwc(const float* g, int64_t B, int H, int W, int C, float* dx, isx_stream_t stream);
 
+/* Backward of isx_boxpool_s1_nhwc, the stride-1 average pool in front of the convolutionalised classifier of TuneClassifSub (model/siamese.py:67-71
+ * AvgPool2d(feature_size2d, stride=1)), without the ReLU mask of the block below.  With Ho = H-kh+1, Wo = W-kw+1:
+ *   dx[b][i][j][c] = ( sum_{p = max(0,i-kh+1)}^{min(Ho-1,i)} sum_{q = max(0,j-kw+1)}^{min(Wo-1,j)} g[b][p][q][c] ) / (kh * kw)
+ * p outside, q inside, both ascending, fp32 adds from +0, ONE division at the end; kh == H and kw == W: the bits of isx_gap_bwd_nhwc.
+ * g: (B,Ho,Wo,C); dx: (B,H,W,C); C % 4 == 0, 16-byte aligned, Ho * Wo * 16 bytes within the 64 KB LDS staging; an image's rows depend on no
+ * other image. */
+int isx_boxpool_s1_bwd_nhwc(const float* g, int64_t B, int C, int H, int W, int kh, int kw, float* dx, isx_stream_t stream);
+
 /* Per-leaf weight gradient of the classifier Linear(2048 -> num_classes) (model/siamese.py:28-32; autograd forms it once per micro-batch,
  * utils/train_general.py:51-61): dw[l][n][k] = sum_{r < R} dy[l R + r][n] * x[l R + r][k], ONE fp32 fma chain from +0 over the leaf's rows in
  * row order, never split.  dy: (leaves * R, N), x: (leaves * R, K), dw: (leaves, N, K); any N, K % 4 == 0. */

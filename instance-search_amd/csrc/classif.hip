@@ -99,6 +99,39 @@ __global__ __launch_bounds__(256) void gap_bwd_nhwc_kernel(const float4* __restr
     }
 }
 
+// Backward of the stride-1 box pool (boxpool_s1_nhwc_kernel of pool.hip), channels-last: g (B,Ho,Wo,C) -> dx (B,H,W,C).  Same layout as the
+// forward: one workgroup per (image, slice of CS channels), the slice of the whole gradient map staged in LDS with 16-B loads, a thread owns 4
+// consecutive channels of an INPUT pixel and adds the windows that cover it -- rows p ascending outside, columns q ascending inside, fp32 from
+// +0 -- then divides ONCE by kh * kw (the forward forms s / div the same way).  No atomics, no dependence on other images.
+__global__ __launch_bounds__(256) void boxpool_s1_bwd_nhwc_kernel(const float* __restrict__ g, int C, int H, int W, int kh, int kw, int CS,
+                                                                  float* __restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int Ho = H - kh + 1, Wo = W - kw + 1, HWi = H * W, HWo = Ho * Wo;
+    const int q4 = CS >> 2;                                      // float4 per pixel of the slice
+    const int c0 = blockIdx.x * CS;
+    const float* src = g + (int64_t)blockIdx.y * HWo * C + c0;
+    float4* l4 = reinterpret_cast<float4*>(lds);
+    for (int i = threadIdx.x; i < HWo * q4; i += 256) {
+        const int p = i / q4, cq = i - p * q4;
+        l4[i] = *reinterpret_cast<const float4*>(src + (int64_t)p * C + cq * 4);
+    }
+    __syncthreads();
+    const float div = (float)(kh * kw);
+    float* dst = dx + (int64_t)blockIdx.y * HWi * C + c0;
+    for (int o = threadIdx.x; o < HWi * q4; o += 256) {
+        const int pix = o / q4, cq = o - pix * q4, i = pix / W, j = pix - i * W;
+        const int p0 = i - kh + 1 > 0 ? i - kh + 1 : 0, p1 = i < Ho - 1 ? i : Ho - 1;
+        const int q0 = j - kw + 1 > 0 ? j - kw + 1 : 0, q1 = j < Wo - 1 ? j : Wo - 1;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int p = p0; p <= p1; ++p)
+            for (int q = q0; q <= q1; ++q) {
+                const float4 v = l4[(p * Wo + q) * q4 + cq];
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            }
+        *reinterpret_cast<float4*>(dst + (int64_t)pix * C + cq * 4) = make_float4(s.x / div, s.y / div, s.z / div, s.w / div);
+    }
+}
+
 // dw[l][n][k] = sum_r dy[l R + r][n] * x[l R + r][k]: ONE fp32 fma chain from +0 over the leaf's rows in row order, never split.
 // A thread owns 4 consecutive k of 4 consecutive n (16 chains); a block covers 16 n x 256 k of one leaf.  R is 8..64: R / 2 flop per byte
 // written, and gfx950's fp32 MFMA rate equals its vector rate, so the chains run on the vector ALU, where fmaf IS the canonical chain,
@@ -179,6 +212,23 @@ ISX_API int isx_gap_bwd_nhwc(const float* g, int64_t B, int H, int W, int C, flo
     const unsigned grid = (unsigned)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
     hipLaunchKernelGGL(gap_bwd_nhwc_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4*)g, total4, H * W, C / 4, (float)(H * W), (float4*)dx);
     ISX_CHECK_LAUNCH("isx_gap_bwd_nhwc");
+    return ISX_OK;
+}
+
+ISX_API int isx_boxpool_s1_bwd_nhwc(const float* g, int64_t B, int C, int H, int W, int kh, int kw, float* dx, isx_stream_t stream) {
+    ISX_REQUIRE(B >= 0 && B < 65536 && C > 0 && H > 0 && W > 0 && kh > 0 && kw > 0 && kh <= H && kw <= W && (int64_t)H * W < (1 << 24),
+                "isx_boxpool_s1_bwd_nhwc: bad shape B=%lld C=%d H=%d W=%d k=%dx%d", (long long)B, C, H, W, kh, kw);
+    ISX_REQUIRE(C % 4 == 0, "isx_boxpool_s1_bwd_nhwc: C=%d must be a multiple of 4", C);
+    if (B == 0) return ISX_OK;
+    ISX_REQUIRE(g && dx && g != dx, "isx_boxpool_s1_bwd_nhwc: null or aliased pointer");
+    ISX_REQUIRE((((uintptr_t)g | (uintptr_t)dx) % 16) == 0, "isx_boxpool_s1_bwd_nhwc: misaligned pointer (16 bytes)");
+    const size_t HWo = (size_t)(H - kh + 1) * (W - kw + 1);
+    int CS = 64;                                                  // channels per workgroup: the slice of the gradient map must fit 64 KB of LDS
+    while (CS > 4 && (C % CS != 0 || HWo * CS * 4 > 64 * 1024)) CS >>= 1;
+    ISX_REQUIRE(C % CS == 0 && HWo * CS * 4 <= 64 * 1024, "isx_boxpool_s1_bwd_nhwc: a %dx%d map does not fit the LDS staging", H, W);
+    hipLaunchKernelGGL(boxpool_s1_bwd_nhwc_kernel, dim3((unsigned)(C / CS), (unsigned)B), dim3(256), HWo * CS * 4, (hipStream_t)stream, g, C, H, W, kh, kw,
+                       CS, dx);
+    ISX_CHECK_LAUNCH("isx_boxpool_s1_bwd_nhwc");
     return ISX_OK;
 }
 

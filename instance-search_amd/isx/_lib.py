@@ -88,6 +88,7 @@ _SIGNATURES = {
     "isx_softmax_xent_bwd": (C.c_int, [VP, VP, I64, I32, F32, VP, VP, VP]),
     "isx_softmax_xent_leaves": (C.c_int, [VP, VP, I32, I32, I32, F32, F32, VP, VP, VP]),
     "isx_gap_bwd_nhwc": (C.c_int, [VP, I64, I32, I32, I32, VP, VP]),
+    "isx_boxpool_s1_bwd_nhwc": (C.c_int, [VP, I64, I32, I32, I32, I32, I32, VP, VP]),
     "isx_linear_wgrad_leaves": (C.c_int, [VP, VP, I32, I32, I32, I32, VP, VP]),
     "isx_comm_unique_id_bytes": (C.c_int, []),
     "isx_comm_unique_id": (C.c_int, [VP]),

@@ -889,6 +889,23 @@ def gap_bwd_nhwc(g, H, W):
     return dx
 
 
+def boxpool_s1_bwd_nhwc(g, H, W, kh, kw):
+    """Backward of boxpool_s1_nhwc: g (B, C, H-kh+1, W-kw+1) channels-last -> channels-last (B, C, H, W), every input pixel the sum of the windows
+    that cover it (rows, then columns, ascending) divided once by kh * kw (isx_boxpool_s1_bwd_nhwc)."""
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32 and g.dim() == 4):
+        raise _lib.IsxError("g must be a float32 CUDA tensor (B, C, Ho, Wo) (libisx has no CPU path)")
+    _on_current_device(g, "g")
+    B, Cc, Ho, Wo = g.shape
+    if Ho != H - kh + 1 or Wo != W - kw + 1:
+        raise _lib.IsxError("boxpool_s1_bwd_nhwc: g %s is not the %dx%d pooling of a %dx%d map" % (tuple(g.shape), kh, kw, H, W))
+    gl = g.permute(0, 2, 3, 1)
+    if not gl.is_contiguous():
+        gl = gl.contiguous()
+    dx = torch.empty((B, H, W, Cc), device=g.device, dtype=torch.float32)
+    check(lib().isx_boxpool_s1_bwd_nhwc(gl.data_ptr(), B, Cc, H, W, kh, kw, dx.data_ptr(), _stream()), "isx_boxpool_s1_bwd_nhwc")
+    return dx.permute(0, 3, 1, 2)
+
+
 def linear_wgrad_leaves(dy, x, leaves):
     """dw[l] = dy_l^T x_l for `leaves` consecutive groups of rows, one row-ordered fp32 fma chain per element (isx_linear_wgrad_leaves).
     dy: (leaves * R, N), x: (leaves * R, K) -> (leaves, N, K)."""

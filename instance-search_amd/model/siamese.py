@@ -185,13 +185,55 @@ class TuneClassifSub(TuneClassif):
         _convolutionalize_classifier(self.classifier, feature_size2d, has_reduc)
 
     def forward_single(self, x):
+        if self.training and torch.is_grad_enabled() and x.is_cuda:
+            return self.head_rows(self._split_trunk()(self.features, x))     # training on the GPU: frozen prefix on the folded HIP trunk (_SplitTrunk)
         return self.classifier(self.feature_reduc(self.features(x)))
-
-    def trunk_precomputable(self):
-        return False                                         # multi-scale score maps: none of TuneClassif's one-branch training hooks apply
 
     def forward(self, *scales):
         return [self.forward_single(x) for x in scales]
+
+    # ---- hooks of the training step (utils/train_general._Stepper._scales_batched): one branch PER SCALE of an image, each of its own spatial
+    # size (train/classif_regions.py).  trunk_precomputable and suffix_engine are TuneClassif's. -----------------------------------------------
+    def precompute_trunk(self, *scales, cache=False):
+        """The frozen trunk prefix of every scale's image batch, one launch of the folded inference trunk PER SCALE (the scales differ in size):
+        a tuple of feature tensors of different spatial size, or None when the trunk has to run inside the step (see TuneClassif).  The
+        prefix-feature table of a resident set (`cache`) holds one size only: not used here."""
+        trunk = self._split_trunk()
+        if not self.training or not scales or not all(x.is_cuda and x.dtype == torch.float32 for x in scales):
+            return None
+        if not trunk.usable(self.features, scales[0]) or len(set(x.size(0) for x in scales)) != 1:
+            return None
+        return tuple(trunk.prefix(self.features, x)[0] for x in scales)
+
+    def classif_head_engine(self):
+        return None                                          # TuneClassif's whole-map tail: the window is smaller than the map here
+
+    def region_classif_engine(self):
+        """The libisx engine of box pool -> 1x1 classifier -> cross-entropy over the windows for all local micro-batches of one scale
+        (isx/region_classif.py), when the step may drive it by hand: the conditions of TuneClassif.classif_head_engine, same switch
+        (ISX_CLASSIF_ENGINE=0: None, the tail stays on torch autograd)."""
+        trunk = self._split_trunk()
+        if not (CLASSIF_ENGINE and self.trunk_precomputable() and trunk.folded is not None):
+            return None
+        mods = list(self.features)[trunk.split:]
+        if any(p.requires_grad for m in mods for p in m.parameters()) and self.suffix_engine() is None:
+            return None
+        from isx.region_classif import RegionClassifEngine
+        if not RegionClassifEngine.applicable(self):
+            return None
+        eng = self.__dict__.get("_region_classif_engine")
+        if eng is None or eng.conv is not self.classifier[0] or eng.pool is not self.feature_reduc[0]:
+            eng = self.__dict__["_region_classif_engine"] = RegionClassifEngine(self)
+        return eng
+
+    def head_rows(self, f, n_branches=1):
+        """box pool + convolutionalised classifier on the trunk output of one scale (torch autograd when f carries a graph): the class-score map"""
+        return self.classifier(self.feature_reduc(f))
+
+    def forward_features(self, *feats):
+        """forward() of training mode on precomputed prefix features: trainable suffix + pool + classifier, scale by scale"""
+        split = self._split_trunk().split
+        return [self.head_rows(_SplitTrunk.suffix(self.features, f, split)) for f in feats]
 
 
 # A/B switch: ISX_SPLIT_TRUNK=0 (or model.siamese.SPLIT_TRUNK = False) runs the training trunk as plain `features(x)` -- the

@@ -446,16 +446,31 @@ def load_training_sets(P, dataset_full, labels):
     return ref_set, ref_set, test_set
 
 
+def parse_scales(arg):
+    """'0,224' -> [None, 224]: the scale list of train.classif_regions (0 = the image as is, n > 0 = shorter side to n pixels).  Empty entries,
+    negative sizes and a scale given twice are refused (a repeated scale would train on the same windows twice)."""
+    out = []
+    for v in arg.split(','):
+        if not v.strip().isdigit():
+            raise ValueError('scales are a comma list of non-negative integers (0 = as is), got %r' % (v,))
+        out.append(int(v) or None)
+    if len(set(out)) != len(out):
+        raise ValueError('every scale may be given once, got %r' % (arg,))
+    return out
+
+
 def training_cli(argv, P, run, what):
     """`python -m train.<approach> --dataset=<folder | synthetic:...> [--model=] [--device=] [--epochs=] [--classif-model=] [--preload-net=]
-    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=]`: the reference's training scripts take everything from their
+    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=] [--bn-model=] [--scales=]`
+    (--scales: comma list of shorter-side sizes of train.classif_regions, 0 = the image as is): the reference's training scripts take everything from their
     *_p.py file (edit and run); the same fields can be given here instead."""
     import getopt
     import sys
     spec = {'dataset': ('dataset_full', str), 'model': ('cnn_model', str), 'device': ('cuda_device', int), 'epochs': ('train_epochs', int),
             'classif-model': ('classif_model', str), 'preload-net': ('preload_net', str), 'save-dir': ('save_dir', str),
             'feature-dim': ('feature_dim', int), 'batch-size': ('train_batch_size', int), 'micro-batch': ('train_micro_batch', int),
-            'lr': ('train_lr', float), 'seed': ('train_seed', int), 'loss-int': ('train_loss_int', int)}
+            'lr': ('train_lr', float), 'seed': ('train_seed', int), 'loss-int': ('train_loss_int', int), 'bn-model': ('bn_model', str),
+            'scales': ('train_sub_scales', parse_scales)}
     try:
         opts, _ = getopt.getopt(argv, '', ['help'] + [k + '=' for k in spec])
     except getopt.GetoptError as e:
@@ -466,7 +481,11 @@ def training_cli(argv, P, run, what):
             print('usage: python -m %s %s' % (what, ' '.join('[--%s=]' % k for k in spec)))
             sys.exit()
         field, typ = spec[opt[2:]]
-        setattr(P, field, typ(arg))
+        try:
+            setattr(P, field, typ(arg))
+        except ValueError as e:
+            print('%s=%s: %s\nusage: python -m %s %s' % (opt, arg, e, what, ' '.join('[--%s=]' % k for k in spec)))
+            sys.exit(2)
     if not getattr(P, 'dataset_full', None):
         print('no dataset: give --dataset=<folder> (or synthetic:<dataset id>[:n=..][:q=..][:labels=..]) or set P.dataset_full')
         sys.exit(2)

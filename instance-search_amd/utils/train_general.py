@@ -274,6 +274,61 @@ class _Stepper(object):
                 eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
         return flat_all, losses
 
+    @staticmethod
+    def _scales_fit(eng, rce, feats, k):
+        """True when every scale's trunk output holds at least one window and a micro-batch of k images has at most the 8192 window rows
+        isx_softmax_xent_leaves takes per leaf (decided from the shapes alone: the same answer on every rank)."""
+        from isx.region_classif import MAX_ROWS_PER_LEAF
+        kh, kw = rce.window()
+        for f in feats:
+            h, w = f.shape[2], f.shape[3]
+            for convs, _ in (eng.layers if eng is not None else ()):
+                s = convs[1].stride
+                h, w = (h - 1) // s + 1, (w - 1) // s + 1
+            if h < kh or w < kw or k * (h - kh + 1) * (w - kw + 1) > MAX_ROWS_PER_LEAF:
+                return False
+        return True
+
+    def _scales_batched(self, eng, rce, mine, offsets, mini_size, pre):
+        """Sub-region classifier training (train/classif_regions.py): `pre` holds one prefix feature tensor PER SCALE of the local images, each of
+        its own spatial size, and the training script declared its loss to be the cross-entropy criterion over every window of every scale
+        (`create_loss.region_cross_entropy = criterion`).  Scale by scale, in the order of the item's scale list: all local micro-batches through
+        the trunk suffix (isx/suffix.py), box pool -> classifier -> cross-entropy over the windows (isx/region_classif.py) and the suffix backward,
+        gradients kept apart per micro-batch as in _leaves_batched.  Scale 0 writes the leaves' flat gradient rows, every further scale a buffer of
+        its own that is then added: a leaf's gradient is the fp32 SUM OF ITS SCALES' GRADIENTS IN SCALE ORDER, each of them bit for bit what a
+        pass over that leaf alone produces -- and what a rank of a P-rank run computes.  A leaf's loss is summed over the scales the same way.
+        Returns (flat_all (L, total), losses)."""
+        P = self.P
+        feats, targets_all = pre
+        k, L, S = len(mine[0]), len(mine), len(feats)
+        flat = self.flat.flat
+        flat_all = torch.zeros((L, flat.numel()), dtype=flat.dtype, device=flat.device)
+        xent = self.make_loss.region_cross_entropy
+        labels = torch.cat([targets_all[0][o:o + k] for o in offsets], 0)
+        share = k / float(mini_size)
+        scale_b = share / S if P.train_loss_avg else 1.0
+        total = None
+        for s, f in enumerate(feats):
+            part = flat_all if s == 0 else torch.zeros_like(flat_all)
+            with _phase("suffix_forward"):
+                x_all = torch.cat([f[o:o + k] for o in offsets], 0)
+                y_all, saved = eng.forward(x_all) if eng is not None else (x_all, None)
+            k_s = k * rce.rows_per_image(y_all.shape[2], y_all.shape[3])            # window rows of a leaf at this scale
+            with _phase("heads"):
+                per_leaf, dy_all = rce.step(y_all, labels, L, (1.0 / k_s) if xent.size_average else 1.0, scale_b, part, self.flat.slices,
+                                            need_dy=eng is not None)
+                if xent.size_average:
+                    per_leaf = per_leaf / k_s
+                if P.train_loss_avg:
+                    per_leaf = per_leaf * scale_b
+                total = per_leaf if total is None else total + per_leaf
+            if eng is not None:
+                with _phase("suffix_backward"):
+                    eng.backward(saved, dy_all, leaves=L, leaf_grads=(part, self.flat.slices))
+            if s > 0:
+                flat_all += part
+        return flat_all, list(total.unbind(0))
+
     def _slice(self, mini_batch):
         """This rank's micro-batches of a mini-batch: (leaves, first leaf index, one past the last, their items in order, row offset of each leaf)."""
         from isx import dp
@@ -356,16 +411,41 @@ class _Stepper(object):
             for sh in sink.shards.values():
                 sh.begin_step(len(mine))
             sink.leaf_ids = list(range(lo, hi))
-            eng = head = chead = None
+            eng = head = chead = rce = None
             batched = getattr(self.P, 'train_suffix_batched', True)
+            # a net whose branches are the SCALES of an image (TuneClassifSub: feature maps of different size per branch) takes the scales
+            # route below or the generic one, never _leaves_batched (which stacks the branches)
+            scales_net = hasattr(self.net, 'region_classif_engine')
             # batched engines need equal micro-batches; decided from the MINI-BATCH (n % mb == 0: every leaf of every rank has mb triplets), not from
             # this rank's leaves, so that every rank and the single-process run take the same numeric path (round-4 ADVICE)
-            if self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched:
+            if self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched and not scales_net:
                 eng = getattr(self.net, 'suffix_engine', lambda: None)()
                 head = getattr(self.net, 'head_engine', lambda: None)()
                 if getattr(self.make_loss, 'cross_entropy', None) is not None:
                     chead = getattr(self.net, 'classif_head_engine', lambda: None)()     # classification fine-tuning (TuneClassif), else None
-            if eng is not None or head is not None or chead is not None:
+            elif (self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched
+                    and getattr(self.make_loss, 'region_cross_entropy', None) is not None):
+                rce = self.net.region_classif_engine()                                   # sub-region classifier training (TuneClassifSub), else None
+                if rce is not None:
+                    eng = self.net.suffix_engine()
+                    if not self._scales_fit(eng, rce, pre[0], mb):
+                        eng = rce = None
+            if rce is not None:
+                if batched == "leaf":                # test mode, as below
+                    parts = [self._scales_batched(eng, rce, [mine[j]], [offsets[j]], n, pre) for j in range(len(mine))]
+                    flat_all = torch.cat([p[0] for p in parts], 0)
+                    losses = [l for p in parts for l in p[1]]
+                else:
+                    flat_all, losses = self._scales_batched(eng, rce, mine, offsets, n, pre)
+                if flat_all.is_cuda and 1 <= hi - lo <= 16:
+                    from isx import ops
+                    self.flat.attach_all()
+                    ops.tree_sum_rows(flat_all, out=self.flat.flat)
+                else:
+                    self.flat.put(dp.tree_sum(lo, hi, lambda i: flat_all[i - lo]))
+                if self.exchange is not None:
+                    self.exchange.allreduce_(self.flat.flat)
+            elif eng is not None or head is not None or chead is not None:
                 if batched == "leaf":                # test mode: the same machinery one micro-batch at a time (what a rank with ONE leaf runs)
                     parts = [self._leaves_batched(eng, head, [mine[j]], [offsets[j]], n, pre, sink, chead) for j in range(len(mine))]
                     flat_all = torch.cat([p[0] for p in parts], 0)
