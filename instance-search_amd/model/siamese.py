@@ -149,9 +149,10 @@ class TuneClassif(nn.Module):
         return eng if eng and SuffixEngine.applicable(mods) else None
 
     def classif_head_engine(self):
-        """The libisx engine of pool -> Linear -> cross-entropy for all local micro-batches of a training step at once (isx/classif_head.py), when
-        the step may drive it by hand: a single Linear behind a whole-map average pool (the ResNets), GPU training with a precomputable trunk
-        whose trainable part (if any) runs on the suffix engine.  ISX_CLASSIF_ENGINE=0: None (the tail stays on torch autograd)."""
+        """The libisx engine of pool -> classifier -> cross-entropy for all local micro-batches of a training step at once (isx/classif_head.py),
+        when the step may drive it by hand: a single classifier layer behind a single average pool (the ResNets; TuneClassifSub: the box pool
+        and the 1x1 classifier over the windows of one scale), GPU training with a precomputable trunk whose trainable part (if any) runs on
+        the suffix engine.  ISX_CLASSIF_ENGINE=0: None (the tail stays on torch autograd)."""
         trunk = self._split_trunk()
         if not (CLASSIF_ENGINE and self.trunk_precomputable() and trunk.folded is not None):
             return None
@@ -162,7 +163,7 @@ class TuneClassif(nn.Module):
         if not ClassifHeadEngine.applicable(self):
             return None
         eng = self.__dict__.get("_classif_head_engine")
-        if eng is None or eng.lin is not self.classifier[0] or eng.pool is not self.feature_reduc[0]:
+        if eng is None or eng.cls is not self.classifier[0] or eng.pool is not self.feature_reduc[0]:
             eng = self.__dict__["_classif_head_engine"] = ClassifHeadEngine(self)
         return eng
 
@@ -177,6 +178,8 @@ class TuneClassif(nn.Module):
 
 
 class TuneClassifSub(TuneClassif):
+    branches_are_scales = True      # forward(*scales): feature maps of a different size per branch, which a training step must not stack
+
     def __init__(self, net, num_classes, feature_size2d, untrained=-1):
         super().__init__(net, num_classes, untrained, reduc=True)
         has_reduc = len(self.feature_reduc) > 0
@@ -192,8 +195,8 @@ class TuneClassifSub(TuneClassif):
     def forward(self, *scales):
         return [self.forward_single(x) for x in scales]
 
-    # ---- hooks of the training step (utils/train_general._Stepper._scales_batched): one branch PER SCALE of an image, each of its own spatial
-    # size (train/classif_regions.py).  trunk_precomputable and suffix_engine are TuneClassif's. -----------------------------------------------
+    # ---- hooks of the training step (utils/train_general._Stepper._classif_batched): one branch PER SCALE of an image, each of its own spatial
+    # size (train/classif_regions.py).  trunk_precomputable, suffix_engine and classif_head_engine are TuneClassif's. --------------------------
     def precompute_trunk(self, *scales, cache=False):
         """The frozen trunk prefix of every scale's image batch, one launch of the folded inference trunk PER SCALE (the scales differ in size):
         a tuple of feature tensors of different spatial size, or None when the trunk has to run inside the step (see TuneClassif).  The
@@ -204,27 +207,6 @@ class TuneClassifSub(TuneClassif):
         if not trunk.usable(self.features, scales[0]) or len(set(x.size(0) for x in scales)) != 1:
             return None
         return tuple(trunk.prefix(self.features, x)[0] for x in scales)
-
-    def classif_head_engine(self):
-        return None                                          # TuneClassif's whole-map tail: the window is smaller than the map here
-
-    def region_classif_engine(self):
-        """The libisx engine of box pool -> 1x1 classifier -> cross-entropy over the windows for all local micro-batches of one scale
-        (isx/region_classif.py), when the step may drive it by hand: the conditions of TuneClassif.classif_head_engine, same switch
-        (ISX_CLASSIF_ENGINE=0: None, the tail stays on torch autograd)."""
-        trunk = self._split_trunk()
-        if not (CLASSIF_ENGINE and self.trunk_precomputable() and trunk.folded is not None):
-            return None
-        mods = list(self.features)[trunk.split:]
-        if any(p.requires_grad for m in mods for p in m.parameters()) and self.suffix_engine() is None:
-            return None
-        from isx.region_classif import RegionClassifEngine
-        if not RegionClassifEngine.applicable(self):
-            return None
-        eng = self.__dict__.get("_region_classif_engine")
-        if eng is None or eng.conv is not self.classifier[0] or eng.pool is not self.feature_reduc[0]:
-            eng = self.__dict__["_region_classif_engine"] = RegionClassifEngine(self)
-        return eng
 
     def head_rows(self, f, n_branches=1):
         """box pool + convolutionalised classifier on the trunk output of one scale (torch autograd when f carries a graph): the class-score map"""

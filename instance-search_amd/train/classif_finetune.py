@@ -138,7 +138,7 @@ def train_classif(net, train_set, testset_tuple, criterion, optimizer, best_scor
         return criterion(t_out, labels_list[0]), None
 
     # the loss IS the cross-entropy criterion on the class scores: the step may evaluate pool, classifier and loss of all its micro-batches in
-    # one pass (utils/train_general._Stepper._leaves_batched -> isx.classif_head), same values per row
+    # one pass (utils/train_general._Stepper._classif_batched -> isx.classif_head), same values per row
     if type(criterion) is CrossEntropyLoss:
         create_loss.cross_entropy = criterion
 

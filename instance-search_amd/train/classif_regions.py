@@ -3,7 +3,7 @@ test_classif_net (:25-51) and the training of the fully convolutional classifier
 (train_classif_subparts :54-102, main :152-200), whose checkpoint the region-descriptor training starts from (P.classif_model of
 train.siamese_regions).  Descriptor = the class-score vector at the location whose best class score is highest, L2-normalised.  On the GPU the
 frozen trunk prefix runs once per scale and mini-batch on the folded HIP trunk, layer4 on isx.suffix.SuffixEngine and box pool -> classifier ->
-cross-entropy over the windows on isx.region_classif (utils/train_general._Stepper._scales_batched); on the CPU, with BatchNorm learning or for
+cross-entropy over the windows on isx.classif_head (utils/train_general._Stepper._classif_batched); on the CPU, with BatchNorm learning or for
 AlexNet's classifier the step is plain torch autograd."""
 import random
 
@@ -100,7 +100,7 @@ def region_loss(criterion, loss_avg):
         return loss, None
 
     # the loss IS the cross-entropy criterion on the windows of every scale: the step may evaluate pool, classifier and loss of all its
-    # micro-batches in one pass per scale (utils/train_general._Stepper._scales_batched -> isx.region_classif), same values per row
+    # micro-batches in one pass per scale (utils/train_general._Stepper._classif_batched -> isx.classif_head), same values per row
     if type(criterion) is CrossEntropyLoss:
         create_loss.region_cross_entropy = criterion
     return create_loss

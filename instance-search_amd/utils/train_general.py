@@ -134,22 +134,41 @@ class _Stepper(object):
             sh.sync()
 
     # -- one micro-batch ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _rows(targets, total, lo, hi):
+        """Rows lo:hi of every per-item tensor among the targets (the ones with `total` rows); everything else as it is."""
+        return [t[lo:hi] if torch.is_tensor(t) and t.dim() > 0 and t.size(0) == total else t for t in targets]
+
+    def _objective(self, loss, loss2, share):
+        """What a micro-batch holding `share` of the mini-batch adds to the step's objective (reference utils/train_general.py:51-74)."""
+        P = self.P
+        obj = loss * share if P.train_loss_avg else loss
+        if loss2 is not None:
+            obj = obj + P.train_loss2_alpha * (loss2 * share if P.train_loss2_avg else loss2)
+        return obj
+
+    def _leaf_scales(self, criterion, k, share):
+        """For a *_leaves kernel that returns per-leaf SUMS of row losses: the (scale_a, scale_b) it multiplies the gradients by -- the criterion's
+        mean over the leaf's k rows, the leaf's share of the mini-batch -- and the function that scales the sums the same way."""
+        avg, loss_avg = criterion.size_average, self.P.train_loss_avg
+
+        def rescale(per_leaf):
+            if avg:
+                per_leaf = per_leaf / k
+            return per_leaf * share if loss_avg else per_leaf
+        return (1.0 / k) if avg else 1.0, share if loss_avg else 1.0, rescale
+
     def _forward_backward(self, triplets, offset, mini_size, batch_args, pre, arm=False):
         if pre is not None:
             # prefix features of the whole local slice were computed in one launch (frozen trunk prefix): this micro-batch takes its rows
             feats, targets_all = pre
             n = len(triplets)
             out = self.net.forward_features(*[f[offset:offset + n] for f in feats])
-            targets = [t[offset:offset + n] if torch.is_tensor(t) and t.dim() > 0 and t.size(0) == feats[0].size(0) else t for t in targets_all]
-            loss, loss2 = self.make_loss(out, targets)
+            loss, loss2 = self.make_loss(out, self._rows(targets_all, feats[0].size(0), offset, offset + n))
         else:
             inputs, targets = self.make_batch(triplets, len(triplets), **batch_args)
             loss, loss2 = self.make_loss(self.net(*inputs), targets)
-        P = self.P
-        share = len(triplets) / float(mini_size)
-        obj = loss * share if P.train_loss_avg else loss
-        if loss2 is not None:
-            obj = obj + P.train_loss2_alpha * (loss2 * share if P.train_loss2_avg else loss2)
+        obj = self._objective(loss, loss2, len(triplets) / float(mini_size))
         if arm:
             self.flat.arm()                          # all-reduce path: exchange buckets as this last backward fills them
         obj.backward()
@@ -169,18 +188,18 @@ class _Stepper(object):
             return None
         return feats, targets
 
-    def _leaves_batched(self, eng, head, mine, offsets, mini_size, pre, sink, chead=None):
+    def _leaves_batched(self, eng, head, mine, offsets, mini_size, pre, sink):
         """All local micro-batches through the trainable trunk suffix (isx/suffix.py) and -- when `head` is given -- the descriptor head
         (isx/head.py) in ONE forward and ONE backward each, their gradients kept apart per micro-batch.  Every row is computed exactly as in
         a launch of its own, per-leaf sums run over the leaf's rows / pixels in order: each leaf's flat gradient is bit for bit what a pass
         over that leaf alone produces -- and what a rank of a P-rank run computes.  The loss is the training script's own callback,
         evaluated per micro-batch on its rows.  Without `head` the head runs micro-batch by micro-batch under torch autograd on its rows of
-        the suffix output.  `chead` (classification fine-tuning, isx/classif_head.py): pool, classifier and cross-entropy of all leaves in one
-        pass instead.  Returns (flat_all (L, total), losses)."""
+        the suffix output.  Returns (flat_all (L, total), losses)."""
         P = self.P
         feats, targets_all = pre
         nb, k, L = len(feats), len(mine[0]), len(mine)
         rows = nb * k
+        share = k / float(mini_size)
         flat = self.flat.flat
         flat_all = torch.zeros((L, flat.numel()), dtype=flat.dtype, device=flat.device)
         with _phase("suffix_forward"):
@@ -191,95 +210,55 @@ class _Stepper(object):
                 y_all, saved = x_all, None                                           # the whole trunk is frozen: nothing to train below the head
         losses = []
 
-        def leaf_loss(out, j):
-            o = offsets[j]
-            targets = [t[o:o + k] if torch.is_tensor(t) and t.dim() > 0 and t.size(0) == feats[0].size(0) else t for t in targets_all]
-            loss, loss2 = self.make_loss(out, targets)
-            share = k / float(mini_size)
-            obj = loss * share if P.train_loss_avg else loss
-            if loss2 is not None:
-                obj = obj + P.train_loss2_alpha * (loss2 * share if P.train_loss2_avg else loss2)
-            obj.backward()
-            losses.append(obj.detach().reshape(-1)[0])
+        def leaf_grads(out_of, x_all):
+            """The script's loss on out_of(leaf j's rows of x_all) under torch autograd, leaf by leaf: the gradient wrt x_all."""
+            dx_all = torch.empty_like(x_all)
+            for j in range(L):
+                x = x_all[j * rows:(j + 1) * rows].detach().requires_grad_(True)
+                loss, loss2 = self.make_loss(out_of(x), self._rows(targets_all, feats[0].size(0), offsets[j], offsets[j] + k))
+                obj = self._objective(loss, loss2, share)
+                obj.backward()
+                losses.append(obj.detach().reshape(-1)[0])
+                if x.grad is None:                       # a loss that does not touch this leaf's rows
+                    dx_all[j * rows:(j + 1) * rows].zero_()
+                else:
+                    dx_all[j * rows:(j + 1) * rows].copy_(x.grad)
+                if head is None:
+                    self.flat.attach_all()
+                    flat_all[j].copy_(flat)                                          # the head's small parameters; the suffix slots are still zero
+                    flat.zero_()
+            return dx_all
 
-        ph = _phase("heads")
-        ph.__enter__()
-        if chead is not None:
-            # classification fine-tuning: the training script declared its loss to be THE cross-entropy criterion on the class scores of the
-            # net's one branch (`create_loss.cross_entropy = criterion`): pool, classifier, loss and their backward for all L micro-batches in
-            # one pass (isx/classif_head.py), the leaf's loss = its rows' losses in row order
-            xent = self.make_loss.cross_entropy
-            labels = torch.cat([targets_all[0][o:o + k] for o in offsets], 0)
-            share = k / float(mini_size)
-            per_leaf, dy_all = chead.step(y_all, labels, L, (1.0 / k) if xent.size_average else 1.0, share if P.train_loss_avg else 1.0,
-                                          flat_all, self.flat.slices, need_dy=eng is not None)
-            if xent.size_average:
-                per_leaf = per_leaf / k
-            if P.train_loss_avg:
-                per_leaf = per_leaf * share
-            losses.extend(per_leaf.unbind(0))
-            ph.__exit__()
-            if eng is not None:
-                with _phase("suffix_backward"):
-                    eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
-            return flat_all, losses
-        if head is not None:
-            from model.siamese import _SplitRows
-            shard = sink.shard_for(head.lin.weight) if sink is not None else None
-            d_all, hctx = head.forward(y_all, shard=shard, leaf_ids=list(sink.leaf_ids) if shard is not None else None)
-            trip = getattr(self.make_loss, 'triplet', None)
-            if trip is not None and nb == 3 and d_all.is_cuda and getattr(P, 'train_loss_batched', True):
-                # the training script declared its loss to be THE triplet criterion on (anchor, positive, negative) and nothing else
-                # (`create_loss.triplet = criterion`): all L micro-batches in one launch (isx_triplet_leaves) -- per row the arithmetic of the
-                # criterion's own kernels, the leaf's loss = its rows' losses in row order -- instead of L x (forward, sum, backward, four copies)
-                from isx import ops
-                share = k / float(mini_size)
-                per_leaf, dd = ops.triplet_leaves(d_all, L, trip.margin, trip.normalized, (1.0 / k) if trip.size_average else 1.0,
-                                                  share if P.train_loss_avg else 1.0)
-                if trip.size_average:
-                    per_leaf = per_leaf / k
-                if P.train_loss_avg:
-                    per_leaf = per_leaf * share
-                losses.extend(per_leaf.unbind(0))
+        with _phase("heads"):
+            if head is None:
+                dy_all = leaf_grads(lambda z: self.net.head_rows(z, nb), y_all)
+            else:
+                from model.siamese import _SplitRows
+                shard = sink.shard_for(head.lin.weight) if sink is not None else None
+                d_all, hctx = head.forward(y_all, shard=shard, leaf_ids=list(sink.leaf_ids) if shard is not None else None)
+                trip = getattr(self.make_loss, 'triplet', None)
+                if trip is not None and nb == 3 and d_all.is_cuda and getattr(P, 'train_loss_batched', True):
+                    # the training script declared its loss to be THE triplet criterion on (anchor, positive, negative) and nothing else
+                    # (`create_loss.triplet = criterion`): all L micro-batches in one launch (isx_triplet_leaves) -- per row the arithmetic of the
+                    # criterion's own kernels, the leaf's loss = its rows' losses in row order -- instead of L x (forward, sum, backward, four copies)
+                    from isx import ops
+                    scale_a, scale_b, rescale = self._leaf_scales(trip, k, share)
+                    per_leaf, dd = ops.triplet_leaves(d_all, L, trip.margin, trip.normalized, scale_a, scale_b)
+                    losses.extend(rescale(per_leaf).unbind(0))
+                else:
+                    dd = leaf_grads(lambda d: _SplitRows.apply(d, nb), d_all)
                 dy_all = head.backward(hctx, dd, L, sink, flat_all, self.flat.slices)
-                ph.__exit__()
-                if eng is not None:
-                    with _phase("suffix_backward"):
-                        eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
-                return flat_all, losses
-            dd = torch.empty_like(d_all)
-            for j in range(L):
-                d = d_all[j * rows:(j + 1) * rows].detach().requires_grad_(True)
-                leaf_loss(_SplitRows.apply(d, nb), j)
-                if d.grad is None:                       # a loss that does not touch this leaf's descriptors
-                    dd[j * rows:(j + 1) * rows].zero_()
-                else:
-                    dd[j * rows:(j + 1) * rows].copy_(d.grad)
-            dy_all = head.backward(hctx, dd, L, sink, flat_all, self.flat.slices)
-        else:
-            dy_all = torch.empty_like(y_all)
-            for j in range(L):
-                z = y_all[j * rows:(j + 1) * rows].detach().requires_grad_(True)
-                leaf_loss(self.net.head_rows(z, nb), j)
-                if z.grad is None:
-                    dy_all[j * rows:(j + 1) * rows].zero_()
-                else:
-                    dy_all[j * rows:(j + 1) * rows].copy_(z.grad)
-                self.flat.attach_all()
-                flat_all[j].copy_(flat)                                              # the head's small parameters; the suffix slots are still zero
-                flat.zero_()
-        ph.__exit__()
         if eng is not None:
             with _phase("suffix_backward"):
                 eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
         return flat_all, losses
 
     @staticmethod
-    def _scales_fit(eng, rce, feats, k):
+    def _scales_fit(eng, chead, feats, k):
         """True when every scale's trunk output holds at least one window and a micro-batch of k images has at most the 8192 window rows
         isx_softmax_xent_leaves takes per leaf (decided from the shapes alone: the same answer on every rank)."""
-        from isx.region_classif import MAX_ROWS_PER_LEAF
-        kh, kw = rce.window()
+        from isx.classif_head import MAX_ROWS_PER_LEAF
+        kh, kw = chead.window()
         for f in feats:
             h, w = f.shape[2], f.shape[3]
             for convs, _ in (eng.layers if eng is not None else ()):
@@ -289,39 +268,32 @@ class _Stepper(object):
                 return False
         return True
 
-    def _scales_batched(self, eng, rce, mine, offsets, mini_size, pre):
-        """Sub-region classifier training (train/classif_regions.py): `pre` holds one prefix feature tensor PER SCALE of the local images, each of
-        its own spatial size, and the training script declared its loss to be the cross-entropy criterion over every window of every scale
-        (`create_loss.region_cross_entropy = criterion`).  Scale by scale, in the order of the item's scale list: all local micro-batches through
-        the trunk suffix (isx/suffix.py), box pool -> classifier -> cross-entropy over the windows (isx/region_classif.py) and the suffix backward,
-        gradients kept apart per micro-batch as in _leaves_batched.  Scale 0 writes the leaves' flat gradient rows, every further scale a buffer of
-        its own that is then added: a leaf's gradient is the fp32 SUM OF ITS SCALES' GRADIENTS IN SCALE ORDER, each of them bit for bit what a
-        pass over that leaf alone produces -- and what a rank of a P-rank run computes.  A leaf's loss is summed over the scales the same way.
-        Returns (flat_all (L, total), losses)."""
-        P = self.P
+    def _classif_batched(self, eng, chead, xent, mine, offsets, mini_size, pre):
+        """Classifier training whose script declared its loss to be THE cross-entropy criterion `xent` on the class scores of every branch:
+        classification fine-tuning (train/classif_finetune.py, `create_loss.cross_entropy = criterion`: one branch) and sub-region classifier
+        training (train/classif_regions.py, `create_loss.region_cross_entropy = criterion`: one branch PER SCALE of the local images, `pre`
+        holding a prefix feature tensor of its own spatial size for each, the loss taken over every window of every scale).  Scale by scale, in
+        the order of the item's scale list: all local micro-batches through the trunk suffix (isx/suffix.py), pool -> classifier ->
+        cross-entropy over the windows (isx/classif_head.py) and the suffix backward, gradients kept apart per micro-batch as in
+        _leaves_batched.  Scale 0 writes the leaves' flat gradient rows, every further scale a buffer of its own that is then added: a leaf's
+        gradient is the fp32 SUM OF ITS SCALES' GRADIENTS IN SCALE ORDER, each of them bit for bit what a pass over that leaf alone produces --
+        and what a rank of a P-rank run computes.  A leaf's loss is summed over the scales the same way.  Returns (flat_all (L, total), losses)."""
         feats, targets_all = pre
         k, L, S = len(mine[0]), len(mine), len(feats)
         flat = self.flat.flat
         flat_all = torch.zeros((L, flat.numel()), dtype=flat.dtype, device=flat.device)
-        xent = self.make_loss.region_cross_entropy
         labels = torch.cat([targets_all[0][o:o + k] for o in offsets], 0)
-        share = k / float(mini_size)
-        scale_b = share / S if P.train_loss_avg else 1.0
         total = None
         for s, f in enumerate(feats):
             part = flat_all if s == 0 else torch.zeros_like(flat_all)
             with _phase("suffix_forward"):
                 x_all = torch.cat([f[o:o + k] for o in offsets], 0)
                 y_all, saved = eng.forward(x_all) if eng is not None else (x_all, None)
-            k_s = k * rce.rows_per_image(y_all.shape[2], y_all.shape[3])            # window rows of a leaf at this scale
+            # the leaf's window rows at this scale; its share of the mini-batch, the scales averaged
+            scale_a, scale_b, rescale = self._leaf_scales(xent, k * chead.rows_per_image(y_all.shape[2], y_all.shape[3]), k / float(mini_size) / S)
             with _phase("heads"):
-                per_leaf, dy_all = rce.step(y_all, labels, L, (1.0 / k_s) if xent.size_average else 1.0, scale_b, part, self.flat.slices,
-                                            need_dy=eng is not None)
-                if xent.size_average:
-                    per_leaf = per_leaf / k_s
-                if P.train_loss_avg:
-                    per_leaf = per_leaf * scale_b
-                total = per_leaf if total is None else total + per_leaf
+                per_leaf, dy_all = chead.step(y_all, labels, L, scale_a, scale_b, part, self.flat.slices, need_dy=eng is not None)
+                total = rescale(per_leaf) if total is None else total + rescale(per_leaf)
             if eng is not None:
                 with _phase("suffix_backward"):
                     eng.backward(saved, dy_all, leaves=L, leaf_grads=(part, self.flat.slices))
@@ -384,7 +356,7 @@ class _Stepper(object):
             a = self._ahead = (start, len(groups), len(groups[0]), feats, targets, len(items))
         g, m = (start - a[0]) // n, a[2]
         feats = tuple(f[g * m:(g + 1) * m] for f in a[3])
-        targets = [t[g * m:(g + 1) * m] if torch.is_tensor(t) and t.dim() > 0 and t.size(0) == a[5] else t for t in a[4]]
+        targets = self._rows(a[4], a[5], g * m, (g + 1) * m)
         if g == a[1] - 1:
             self._ahead = None                   # last user: the block is freed with this step
         return feats, targets
@@ -411,61 +383,41 @@ class _Stepper(object):
             for sh in sink.shards.values():
                 sh.begin_step(len(mine))
             sink.leaf_ids = list(range(lo, hi))
-            eng = head = chead = rce = None
-            batched = getattr(self.P, 'train_suffix_batched', True)
-            # a net whose branches are the SCALES of an image (TuneClassifSub: feature maps of different size per branch) takes the scales
-            # route below or the generic one, never _leaves_batched (which stacks the branches)
-            scales_net = hasattr(self.net, 'region_classif_engine')
+            batched = getattr(P, 'train_suffix_batched', True)
             # batched engines need equal micro-batches; decided from the MINI-BATCH (n % mb == 0: every leaf of every rank has mb triplets), not from
             # this rank's leaves, so that every rank and the single-process run take the same numeric path (round-4 ADVICE)
-            if self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched and not scales_net:
-                eng = getattr(self.net, 'suffix_engine', lambda: None)()
-                head = getattr(self.net, 'head_engine', lambda: None)()
-                if getattr(self.make_loss, 'cross_entropy', None) is not None:
-                    chead = getattr(self.net, 'classif_head_engine', lambda: None)()     # classification fine-tuning (TuneClassif), else None
-            elif (self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched
-                    and getattr(self.make_loss, 'region_cross_entropy', None) is not None):
-                rce = self.net.region_classif_engine()                                   # sub-region classifier training (TuneClassifSub), else None
-                if rce is not None:
-                    eng = self.net.suffix_engine()
-                    if not self._scales_fit(eng, rce, pre[0], mb):
-                        eng = rce = None
-            if rce is not None:
-                if batched == "leaf":                # test mode, as below
-                    parts = [self._scales_batched(eng, rce, [mine[j]], [offsets[j]], n, pre) for j in range(len(mine))]
-                    flat_all = torch.cat([p[0] for p in parts], 0)
-                    losses = [l for p in parts for l in p[1]]
-                else:
-                    flat_all, losses = self._scales_batched(eng, rce, mine, offsets, n, pre)
-                if flat_all.is_cuda and 1 <= hi - lo <= 16:
-                    from isx import ops
-                    self.flat.attach_all()
-                    ops.tree_sum_rows(flat_all, out=self.flat.flat)
-                else:
-                    self.flat.put(dp.tree_sum(lo, hi, lambda i: flat_all[i - lo]))
-                if self.exchange is not None:
-                    self.exchange.allreduce_(self.flat.flat)
-            elif eng is not None or head is not None or chead is not None:
-                if batched == "leaf":                # test mode: the same machinery one micro-batch at a time (what a rank with ONE leaf runs)
-                    parts = [self._leaves_batched(eng, head, [mine[j]], [offsets[j]], n, pre, sink, chead) for j in range(len(mine))]
-                    flat_all = torch.cat([p[0] for p in parts], 0)
-                    losses = [l for p in parts for l in p[1]]
-                else:
-                    flat_all, losses = self._leaves_batched(eng, head, mine, offsets, n, pre, sink, chead)
-                if flat_all.is_cuda and 1 <= hi - lo <= 16:
-                    from isx import ops
-                    self.flat.attach_all()
-                    ops.tree_sum_rows(flat_all, out=self.flat.flat)       # the same tree, one pass over the leaves' rows instead of L - 1 add passes
-                else:
-                    self.flat.put(dp.tree_sum(lo, hi, lambda i: flat_all[i - lo]))
-                if self.exchange is not None:
-                    self.exchange.allreduce_(self.flat.flat)
-            elif self.mode == 'tree':
+            route = None                              # (leaves, their row offsets) -> (flat_all: one flat gradient row per leaf, losses)
+            if self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched:
+                # a net whose branches are the SCALES of an image (TuneClassifSub: feature maps of different size per branch) takes the
+                # classifier route or the generic one, never _leaves_batched (which stacks the branches)
+                scales = getattr(self.net, 'branches_are_scales', False)
+                xent = getattr(self.make_loss, 'region_cross_entropy' if scales else 'cross_entropy', None)
+                chead = getattr(self.net, 'classif_head_engine', lambda: None)() if xent is not None else None
+                if chead is not None or not scales:
+                    eng = getattr(self.net, 'suffix_engine', lambda: None)()
+                    head = getattr(self.net, 'head_engine', lambda: None)()
+                    if chead is not None and self._scales_fit(eng, chead, pre[0], mb):
+                        route = lambda m, o: self._classif_batched(eng, chead, xent, m, o, n, pre)
+                    elif not scales and (eng is not None or head is not None):
+                        route = lambda m, o: self._leaves_batched(eng, head, m, o, n, pre, sink)
+            flat_all = None
+            if route is not None and batched == "leaf":  # test mode: the same machinery one micro-batch at a time (what a rank with ONE leaf runs)
+                parts = [route([mine[j]], [offsets[j]]) for j in range(len(mine))]
+                flat_all = torch.cat([p[0] for p in parts], 0)
+                losses = [l for p in parts for l in p[1]]
+            elif route is not None:
+                flat_all, losses = route(mine, offsets)
+            if self.mode == 'tree':
                 def leaf(i):
                     sink.leaf_ids = [i]
                     losses.append(self._forward_backward(mine[i - lo], offsets[i - lo], n, batch_args, pre))
                     return self.flat.take()
-                self.flat.put(dp.tree_sum(lo, hi, leaf))
+                if flat_all is not None and flat_all.is_cuda and 1 <= hi - lo <= 16:
+                    from isx import ops
+                    self.flat.attach_all()
+                    ops.tree_sum_rows(flat_all, out=self.flat.flat)       # the same tree, one pass over the leaves' rows instead of L - 1 add passes
+                else:
+                    self.flat.put(dp.tree_sum(lo, hi, leaf if flat_all is None else (lambda i: flat_all[i - lo])))
                 if self.exchange is not None:
                     self.exchange.allreduce_(self.flat.flat)
             else:

@@ -115,6 +115,49 @@ def test_linear_wgrad_leaves_is_the_oracles_chain(L, R, N, K):
         assert np.array_equal(dw[l], want), (l, float(np.abs(dw[l] - want).max()))
 
 
+@pytest.mark.parametrize("N", [17, 64])
+def test_one_engine_serves_linear_and_pointwise_conv(N, monkeypatch):
+    """The same weights as nn.Linear behind AvgPool2d(7) and as 1x1 PointwiseConv behind BoxPool((7, 7), stride 1), 4 maps of 7 x 7 in 2 leaves:
+    the same bits, the whole-map backward isx_gap_bwd_nhwc on the pooled gradient in both; a Linear on a map the pool does not span is an error.
+    N = 17 takes the class-padding path, 64 the parameters as they are."""
+    import types
+    from isx import ops
+    from isx._lib import IsxError
+    from isx.classif_head import ClassifHeadEngine
+    from model.siamese import BoxPool, PointwiseConv
+    K, M, L = 64, 4, 2
+    gen = torch.Generator().manual_seed(N)
+    y_all = torch.randn(M, K, 7, 7, generator=gen).cuda().contiguous(memory_format=torch.channels_last)
+    labels = torch.randint(0, N, (M,), generator=gen).cuda()
+    w, b = torch.randn(N, K, generator=gen) * (7.0 / K ** 0.5), torch.randn(N, generator=gen) * 0.1
+    lin, conv = nn.Linear(K, N), PointwiseConv(K, N, 1)
+    with torch.no_grad():
+        lin.weight.copy_(w); lin.bias.copy_(b)
+        conv.weight.copy_(w.view(N, K, 1, 1)); conv.bias.copy_(b)
+    pooled_grads = []
+    gap_bwd = ops.gap_bwd_nhwc
+    monkeypatch.setattr(ops, "gap_bwd_nhwc", lambda g, H, W: (pooled_grads.append((g.clone(), H, W)), gap_bwd(g, H, W))[1])
+
+    def run(pool, cls, y):
+        holder = types.SimpleNamespace(feature_reduc=nn.Sequential(pool), classifier=nn.Sequential(cls).cuda())
+        assert ClassifHeadEngine.applicable(holder)
+        flat_all = torch.zeros(L, N * K + N, device="cuda")
+        per_leaf, dy = ClassifHeadEngine(holder).step(y, labels, L, 0.5, 0.25, flat_all, {cls.weight: (0, N * K), cls.bias: (N * K, N * K + N)}, need_dy=True)
+        return per_leaf, dy, flat_all
+
+    pl_lin, dy_lin, flat_lin = run(nn.AvgPool2d(7), lin, y_all)
+    pl_conv, dy_conv, flat_conv = run(BoxPool((7, 7), stride=1), conv, y_all)
+    assert torch.equal(pl_lin, pl_conv) and torch.equal(dy_lin, dy_conv)
+    assert bool(torch.isfinite(pl_lin).all()) and bool(flat_lin.abs().sum(1).gt(0).all())
+    for l in range(L):
+        assert torch.equal(flat_lin[l], flat_conv[l]), l
+    assert len(pooled_grads) == 2                                                   # both tails took the whole-map backward
+    for (g, H, W), dy in zip(pooled_grads, (dy_lin, dy_conv)):
+        assert g.shape == (M, K) and (H, W) == (7, 7) and torch.equal(dy, gap_bwd(g, 7, 7))
+    with pytest.raises(IsxError):
+        run(nn.AvgPool2d(7), lin, torch.randn(M, K, 9, 9, generator=gen).cuda().contiguous(memory_format=torch.channels_last))
+
+
 # ---- one optimizer step of TuneClassif(ResNet-50) --------------------------------------------------------------------------------------
 def _calibrated(classes, x):
     """TuneClassif(ResNet-50) with seeded weights whose BatchNorm running statistics are those of the images x (one training-mode pass) and whose

@@ -1,5 +1,5 @@
-"""Sub-region classifier training on the GPU (isx_boxpool_s1_bwd_nhwc, isx/region_classif.py, TuneClassifSub's training hooks, the scales route
-of utils/train_general._Stepper): the box-pool backward against its canonical sum bit for bit and against float64 autograd, the engine tail
+"""Sub-region classifier training on the GPU (isx_boxpool_s1_bwd_nhwc, isx/classif_head.py, TuneClassifSub's training hooks, the classifier
+route of utils/train_general._Stepper): the box-pool backward against its canonical sum bit for bit and against float64 autograd, the engine tail
 against float64, one optimizer step of TuneClassifSub(ResNet-50) on two scales against float64 autograd and against the torch-autograd tail, and
 the entry point end to end."""
 import copy
@@ -64,7 +64,7 @@ def test_boxpool_backward_is_the_canonical_sum(B, H, W, kh, kw, C):
     assert not bool(over.any()), (e_gpu, e_cpu)
 
 
-# ---- RegionClassifEngine ----------------------------------------------------------------------------------------------------------------------
+# ---- ClassifHeadEngine behind a box pool ------------------------------------------------------------------------------------------------------
 def _bound(name, p):
     """The relative bounds tests/test_gpu_classif.py and tests/test_gpu_suffix.py assert for the same kinds of tensor: 2e-5 for weight matrices
     (convolution / Linear) and activations' gradients, 1e-5 for the small vectors (BatchNorm weight / bias, the classifier bias)."""
@@ -72,7 +72,7 @@ def _bound(name, p):
 
 
 def test_region_engine_tail_matches_float64_and_leaves_are_independent():
-    from isx.region_classif import RegionClassifEngine
+    from isx.classif_head import ClassifHeadEngine
     from model.siamese import BoxPool, PointwiseConv
     from test_gpu_suffix import _rel
     M, K, N, L = 4, 2048, 17, 4
@@ -84,8 +84,8 @@ def test_region_engine_tail_matches_float64_and_leaves_are_independent():
         conv.weight.copy_(torch.randn(N, K, 1, 1, generator=gen) * (7.0 / K ** 0.5))       # class scores of unit spread
         conv.bias.copy_(torch.randn(N, generator=gen) * 0.1)
     holder = types.SimpleNamespace(feature_reduc=nn.Sequential(BoxPool((7, 7), stride=1)), classifier=nn.Sequential(conv).cuda())
-    assert RegionClassifEngine.applicable(holder)
-    eng = RegionClassifEngine(holder)
+    assert ClassifHeadEngine.applicable(holder)
+    eng = ClassifHeadEngine(holder)
     slices = {conv.weight: (0, N * K), conv.bias: (N * K, N * K + N)}
     scale_a, scale_b = 1.0 / 9, 0.125
 
@@ -191,7 +191,7 @@ def test_scales_step_matches_float64_autograd_and_the_autograd_tail(setup, monke
     for h in hooks:
         h.remove()
     assert nn_utils.TORCH_CONV_CALLS == {} and conv_calls == []              # no convolution of the step ran on torch / MIOpen
-    assert net.region_classif_engine() is not None and net.suffix_engine() is not None
+    assert net.classif_head_engine() is not None and net.suffix_engine() is not None
     after_on = copy.deepcopy(net.state_dict())
     # float64 autograd on the same prefix features with the engine's ReLU pattern pinned; the loss is the reference's formula
     net.load_state_dict(start)
@@ -236,7 +236,7 @@ def test_scales_step_matches_float64_autograd_and_the_autograd_tail(setup, monke
     # engines on vs ISX_CLASSIF_ENGINE=0 (the generic route: pool, classifier and loss per micro-batch on torch autograd): same bounds
     net.load_state_dict(start)
     monkeypatch.setattr(siamese, "CLASSIF_ENGINE", False)
-    assert net.region_classif_engine() is None
+    assert net.classif_head_engine() is None
     loss_off, grads_off = _step(net, xs, y)
     print("region classifier engine on / off: loss %.8f / %.8f" % (loss, loss_off))
     assert abs(loss - loss_off) <= 1e-5 * abs(loss_off)
@@ -263,7 +263,7 @@ def test_entry_point_end_to_end(capsys, tmp_path):
         capsys.readouterr()
         net, _ = cr.run("synthetic:CLICIDE_video_224sq:n=16:q=4:labels=2:size=288:struct=60")
         out = capsys.readouterr().out
-        assert net.region_classif_engine() is not None                                      # the run was on the engines' route
+        assert net.classif_head_engine() is not None                                      # the run was on the engines' route
     finally:
         cr.P.__dict__.clear(); cr.P.__dict__.update(saved); cr.labels[:] = saved_labels
         TC.drop_resident()

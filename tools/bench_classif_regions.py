@@ -4,7 +4,7 @@ hyper-parameters (train/classif_regions_p.py: batch 32, micro-batch 1, SGD momen
 frozen), a resident synthetic 448 x 448 set with its 224 scale.  Two configurations:
 
   engines    frozen prefix once per scale and mini-batch(es) on the folded HIP trunk, layer4 on isx.suffix.SuffixEngine, box pool -> classifier
-             -> cross-entropy over the windows on isx.region_classif (all micro-batches of a scale in one pass)
+             -> cross-entropy over the windows on isx.classif_head (all micro-batches of a scale in one pass)
   autograd   ISX_CLASSIF_ENGINE=0 ISX_SUFFIX_ENGINE=0: layer4, pool, classifier and loss on torch autograd (MIOpen) per micro-batch behind the
              same HIP prefix -- the generic route, the baseline
 
@@ -67,7 +67,7 @@ def run_config(name, args):
     return {"config": name, "micro_batch": args.micro, "steps_per_epoch": steps, "epochs_measured": len(epochs),
             "ms_per_step": 1e3 * med / steps, "ms_per_step_min": 1e3 * min(epochs) / steps, "ms_per_step_max": 1e3 * max(epochs) / steps,
             "images_per_s": steps * P.train_batch_size / med,
-            "region_classif_engine": net.region_classif_engine() is not None, "suffix_engine": net.suffix_engine() is not None}
+            "region_classif_engine": net.classif_head_engine() is not None, "suffix_engine": net.suffix_engine() is not None}
 
 
 def pool_backward(calls):
