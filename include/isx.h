@@ -406,20 +406,28 @@ int isx_l2norm_rows_bwd(const float* x, const float* dy, int64_t B, int64_t D, f
  * s = gamma / sqrt(var + eps).  Every sum has a fixed order: a micro-batch's gradient does not depend on the launch around it. */
 
 /* Gradient of a 1x1 convolution wrt its input: dx = (dz . W' (+ add)) . [mask > 0].  dz: (M, Cout); wt = W'^T as (Cin, Cout)
- * row-major; add (identity-shortcut gradient) and mask (OUTPUT of the ReLU below this convolution): (M, Cin) or NULL; dx: (M, Cin). */
+ * row-major; add (identity-shortcut gradient) and mask (OUTPUT of the ReLU below this convolution): (M, Cin) or NULL; dx: (M, Cin).
+ * Order: dx[m][ci] is ONE k-ordered fp32 fma chain from +0 over co = 0 .. Cout-1 of dz[m][co] * wt[ci][co], whatever tile shape the launch
+ * takes (a k-tile past Cout is zero-filled: fma(0, 0, acc) = acc); then + add[m][ci] (one rounded add), then the mask: mask > 0 ? v : 0 --
+ * the add comes BEFORE the mask, and a mask of -0.0 (like +0.0 and any negative value) gives 0. */
 int isx_conv1x1_dgrad_nhwc(const float* dz, int64_t M, int Cout, const float* wt, int Cin, const float* add, const float* mask,
                            float* dx, isx_stream_t stream);
 
 /* Gradient of a 3x3 convolution (padding 1) wrt its input, as a stride-1 3x3 convolution of dz with
  * wt[ci][kh][kw][co] = w'[co][2-kh][2-kw][ci]; a stride-2 layer passes dz zero-upsampled to the input grid.
- * dz: (B,H,W,Cout), wt: (Cin,3,3,Cout), mask / dx: (B,H,W,Cin); mask as above or NULL.  Cout % 32 == 0. */
+ * dz: (B,H,W,Cout), wt: (Cin,3,3,Cout), mask / dx: (B,H,W,Cin); mask as above or NULL.  Cout % 32 == 0.
+ * Order: dx[b][h][w][ci] is ONE k-ordered fp32 fma chain from +0 over the 9 * Cout terms dz[b][h-1+kh][w-1+kw][co] * wt[ci][kh][kw][co] in
+ * (kh, kw, co) order -- NOT the two-level sum (chunks of 64 terms) of the inference convolutions; a neighbour outside the map enters as
+ * fma(0, w, acc) = acc; then the mask as above (mask > 0 ? v : 0, so -0.0 masks to 0).  mask == NULL: the same chain, unmasked. */
 int isx_conv3x3_dgrad_nhwc(const float* dz, int64_t B, int H, int W, int Cout, const float* wt, int Cin, const float* mask,
                            float* dx, isx_stream_t stream);
 
 /* Gradient of a STRIDE-2 3x3 convolution (padding 1) wrt its input, second half: dcol[p][tap][ci] = sum_co dz[p][co] w'[co][tap][ci] is
  * one GEMM over the OUTPUT pixels (isx_conv1x1_dgrad_nhwc with wt = w' as (9*Cin, Cout)); this entry gathers, for every input pixel, the
  * taps that reach it (1, 2 or 4 of the 9, in (kh, kw) order) and applies the ReLU mask: a quarter of the matrix work of the
- * zero-upsampled form.  dcol: (B*Ho*Wo, 9, Cin); mask (or NULL) / dx: (B,H,W,Cin); Cin % 4 == 0. */
+ * zero-upsampled form.  dcol: (B*Ho*Wo, 9, Cin); mask (or NULL) / dx: (B,H,W,Cin); Cin % 4 == 0.
+ * Order: acc = +0; acc += dcol[(b, (h+1-kh)/2, (w+1-kw)/2)][kh*3+kw][ci] for the taps with (h+1-kh) and (w+1-kw) even and inside the output
+ * grid, kh outer, kw inner (unfused adds); then mask > 0 ? acc : 0.  Each dcol value is itself the one chain over Cout of the GEMM above. */
 int isx_conv3x3_s2_col2im_nhwc(const float* dcol, int64_t B, int H, int W, int Cin, const float* mask, float* dx, isx_stream_t stream);
 
 /* Weight gradient of `leaves` micro-batches in one launch, each split over its pixels: the B images are `leaves` consecutive groups;
@@ -429,7 +437,13 @@ int isx_conv3x3_s2_col2im_nhwc(const float* dcol, int64_t B, int H, int W, int C
  * its first pixel; S and the tile shape depend on the leaf's shape only); isx_bn_fold_backward adds them in split order: a fixed
  * summation tree, no atomics.  taps = 1: 1x1 convolution with `stride` (no padding); taps = 9: 3x3, padding 1, `stride`.
  * x: (B,H,W,Cin), dz: (B,Ho,Wo,Cout), dw: (leaves,S,Cout,taps,Cin) -- per partial the layout of the forward kernels' weights;
- * db: (leaves,S,Cout) or NULL.  Pixels are summed in index order (k-ordered fp32 fma chain).  Cin, Cout % 64 == 0; B % leaves == 0. */
+ * db: (leaves,S,Cout) or NULL.  Pixels are summed in index order (k-ordered fp32 fma chain).  Cin, Cout % 64 == 0; B % leaves == 0.
+ * The split rule: with K the output pixels of ONE leaf, nk = ceil(K / 32) k-tiles of 32 pixels and kt_per = ceil(nk / S), split s owns the
+ * pixels [32 s kt_per, min(K, 32 (s + 1) kt_per)) of its leaf; a split past the last k-tile is EMPTY and writes zeros (dw and db).
+ * The order: dw[l][s][co][tap][ci] is ONE fma chain from +0 over that split's pixels, ascending, of dz[p][co] * x[src(p, tap)][ci], with
+ * src = p for a stride-1 1x1 convolution and (ho * stride + kh - 1, wo * stride + kw - 1), tap = kh * 3 + kw, for 3x3 (ho * stride, wo * stride for a
+ * strided 1x1); a source outside the map enters as fma(dz, 0, acc).  db[l][s][co] is s = 0; s += dz[p][co] over the same pixels, ascending,
+ * with unfused adds.  The tile shape (64x64, or 128x128 once (Cout / 128)(Cin / 128) taps leaves S >= 512) only groups outputs: same bits. */
 int isx_conv_wgrad_splits(int64_t pixels, int Cin, int Cout, int taps);
 int isx_conv_wgrad_nhwc(const float* dz, const float* x, int64_t B, int leaves, int H, int W, int Cin, int Cout, int taps, int stride,
                         float* dw, float* db, isx_stream_t stream);
@@ -442,7 +456,13 @@ int isx_relu_grad(const float* dy, const float* y, int64_t n, float* dz, isx_str
  * parameters: gw_l (+)= d * scale, ggamma_l (+)= (<d, w> - mean * b) * istd, gbeta_l (+)= b, with scale = gamma * istd,
  * istd = 1 / sqrt(running_var + eps).  dwp: (leaves,splits,Cout,taps,Cin); db: (leaves,splits,Cout); w: (Cout,Cin,taps) (nn.Conv2d's
  * layout); gw / ggamma / gbeta: the gradient tensors of leaf 0 (parameter layouts), leaf l at + l * leaf_stride floats (one flat gradient
- * buffer per leaf; leaves == 1: plain tensors); scale, mean, istd: (Cout); accumulate != 0 adds into them (gradient accumulation). */
+ * buffer per leaf; leaves == 1: plain tensors); scale, mean, istd: (Cout); accumulate != 0 adds into them (gradient accumulation).
+ * The order: d = ((p_0 + p_1) + p_2) + ... over the partials in split order, element by element, and b likewise; gw = d * scale[co] (or
+ * prior + that).  <d, w> of an output channel is a fixed reduction by 256 threads: thread t adds the ROUNDED products d_i * w_i (no fma) for
+ * i = t, t + 256, ... from +0; every wave of 64 reduces by the xor butterfly 32, 16, 8, 4, 2, 1; the result is (((0 + wave0) + wave1) +
+ * wave2) + wave3.  The index i runs over the PARAMETER layout (ci, tap) when taps > 1 and taps * (Cin + 1) <= 9 * 513 (3x3 up to Cin = 512: the
+ * row is staged in the LDS) and over the PARTIAL layout (tap, ci) otherwise (every 1x1, 3x3 with Cin > 512); for taps == 1 the two are one.
+ * ggamma = (dot - mean[co] * b) * istd[co], every operation rounded, no fma; gbeta = b.  (tests/_suffix_model.py restates all of this.) */
 int isx_bn_fold_backward(const float* dwp, const float* db, int leaves, int splits, const float* w, const float* scale, const float* mean,
                          const float* istd, int Cout, int Cin, int taps, int accumulate, int64_t leaf_stride, float* gw, float* ggamma,
                          float* gbeta, isx_stream_t stream);

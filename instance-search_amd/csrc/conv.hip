@@ -62,14 +62,16 @@ __global__ __launch_bounds__(256, kWgPerCu128) void conv3x3_tail_kernel(const fl
     }
 }
 
+// grad: the input-gradient instance (one chain over all 9 Cin terms, optional mask) -- chosen by the CALLER, not by the presence of a mask: a
+// gradient without a mask is the same sum as one with it
 template <int TM, int TN, int BK>
 static void launch_conv3x3(const float* x, int64_t M, const float* w, int64_t N, const Conv3x3Geom& g, float* y, const float* bias,
-                           const float* res, int relu, hipStream_t st, const float* mask = nullptr) {
+                           const float* res, int relu, hipStream_t st, const float* mask = nullptr, bool grad = false) {
     TileMap tm;
     tm.m_active = nullptr;
     tm.tiles_m = (int)((M + 64 * TM - 1) / (64 * TM));
     tm.tiles_n = (int)((N + 64 * TN - 1) / (64 * TN));
-    const int64_t split = (TM == 2 && TN == 2 && !mask) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
+    const int64_t split = (TM == 2 && TN == 2 && !grad) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
     if (split > 0) {
         TileMap small;
         small.m_active = nullptr;
@@ -80,7 +82,7 @@ static void launch_conv3x3(const float* x, int64_t M, const float* w, int64_t N,
                            tm, small, split, bias, res, relu);
         return;
     }
-    if (mask) hipLaunchKernelGGL((conv3x3_nhwc_kernel<TM, TN, BK, true>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y, tm, bias,
+    if (grad) hipLaunchKernelGGL((conv3x3_nhwc_kernel<TM, TN, BK, true>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y, tm, bias,
                                  res, relu, mask);
     else hipLaunchKernelGGL((conv3x3_nhwc_kernel<TM, TN, BK, false>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y, tm, bias,
                             res, relu, mask);
@@ -331,9 +333,9 @@ ISX_API int isx_conv3x3_dgrad_nhwc(const float* dz, int64_t B, int H, int W, int
     const int best = pick_tile_cfg(M, N, 0, eff3x3, 0xD);
     hipStream_t st = (hipStream_t)stream;
     switch (best) {
-        case 0: launch_conv3x3<2, 2, 16>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask); break;
-        case 2: launch_conv3x3<2, 1, 32>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask); break;
-        default: launch_conv3x3<1, 1, 32>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask); break;
+        case 0: launch_conv3x3<2, 2, 16>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true); break;
+        case 2: launch_conv3x3<2, 1, 32>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true); break;
+        default: launch_conv3x3<1, 1, 32>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true); break;
     }
     ISX_CHECK_LAUNCH("isx_conv3x3_dgrad_nhwc");
     return ISX_OK;
