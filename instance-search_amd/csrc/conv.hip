@@ -9,6 +9,8 @@
 //    on the main loop of conv3x3_tile.hpp)
 // Launches in 128x128 tiles run the rows past their last whole round of resident workgroups as 64x64 tiles in the same grid
 // (conv3x3_tail_kernel, conv1x1_dual_tail_kernel; conv1x1_tail_kernel in gemm.hip); isx_debug_set_conv_cfg(7) turns that off (A/B).
+// The 128x128 launches of isx_conv3x3_nhwc on small maps number their rows position-major and skip the padding taps (conv3x3_tile.hpp;
+// eligibility and the measured cut-off at kPosMajorMaxP below); isx_debug_set_conv_cfg(8) keeps the pixel-major order (A/B, tests).
 //
 // Reference call sites: the torchvision ResNet `features` trunk built by model/ModelDefinition.py, split by
 // model/nn_utils.py:56-71 and run from model/siamese.py:20,107,151.
@@ -19,33 +21,46 @@
 namespace isx {
 
 // one output tile: main loop + bias / residual / ReLU epilogue.  CHUNK: two-level sum of the inference trunk (gemm_tile.hpp), 0 for the gradient kernels
-template <int TM, int TN, int BK, int CHUNK = kConvChunk>
+// POSMAJ (conv3x3_tile.hpp): m0 is a virtual row -- the tile is output position p of the images b0 .., whose rows of y (and of the residual)
+// are P N floats apart: the same epilogue over the "matrix" of B rows of P N floats that starts at column p N.
+template <int TM, int TN, int BK, int CHUNK = kConvChunk, bool POSMAJ = false>
 __device__ __forceinline__ void conv3x3_tile(float* __restrict__ lds, const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N,
                                              const Conv3x3Geom& g, float* __restrict__ C, int64_t m0, int64_t n0,
                                              const float* __restrict__ bias, const float* __restrict__ res, int relu, const float* __restrict__ mask = nullptr) {
     f32x16 acc[TM][TN];
-    conv3x3_mainloop<TM, TN, BK, false, CHUNK>(lds, x, M, Wt, N, g, m0, n0, acc);
+    if constexpr (POSMAJ) {
+        if (pos_major_tile(g, M, m0).b0 >= M / (g.Ho * g.Wo)) return;       // a tail tile of the last image group without a live row (block-uniform)
+    }
+    conv3x3_mainloop<TM, TN, BK, false, CHUNK, POSMAJ>(lds, x, M, Wt, N, g, m0, n0, acc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm_u = __builtin_amdgcn_readfirstlane(wave >> 1), wn_u = __builtin_amdgcn_readfirstlane(wave & 1);
+    if constexpr (POSMAJ) {
+        const PosMajorTile pt = pos_major_tile(g, M, m0);
+        const int64_t off = (int64_t)pt.p * N, ldc = (int64_t)g.Ho * g.Wo * N;
+        conv_epilogue_buffers<TM, TN, TM * TN < 4 ? 1 : 2>(acc, C + off, res ? res + off : nullptr, bias, relu, pt.b0, pt.B, n0, N, ldc, 64 * TM, wm_u * (32 * TM), wn_u * (32 * TN), lane & 31, lane >> 5);
+        return;
+    }
     // residual / mask look-ahead by register budget: gradient kernels (CHUNK == 0, 116 of 128 VGPRs) one tile at a time, 128x128 inference tiles two
     conv_epilogue_buffers<TM, TN, (CHUNK == 0 || TM * TN < 4) ? 1 : 2>(acc, C, res, bias, relu, m0, M, n0, N, N, 64 * TM, wm_u * (32 * TM), wn_u * (32 * TN), lane & 31, lane >> 5, mask);
 }
 
 // workgroups per CU: 64x64 tiles 6; 128x64 4 (two-level: 126 VGPRs); 128x128 4 with one accumulator set (gradients), 2 with two (64 + 64 accumulator VGPRs)
-template <int TM, int TN, int BK, bool GRAD>
+template <int TM, int TN, int BK, bool GRAD, bool POSMAJ = false>
 __global__ __launch_bounds__(256, TM * TN == 1 ? 6 : (TM * TN == 4 && !GRAD) ? kWgPerCu128 : 4) void conv3x3_nhwc_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N,
                                                            Conv3x3Geom g, float* __restrict__ C, TileMap tm,
                                                            const float* __restrict__ bias, const float* __restrict__ res, int relu, const float* __restrict__ mask) {
     __shared__ float lds[BK * (64 * TM + 64 * TN + 2 * lds_pad(BK))];
     int tile_m, tile_n;
     tile_of_block(tm, tile_m, tile_n);
-    conv3x3_tile<TM, TN, BK, GRAD ? 0 : kConvChunk>(lds, x, M, Wt, N, g, C, (int64_t)tile_m * (64 * TM), (int64_t)tile_n * (64 * TN), bias, res, relu, mask);
+    conv3x3_tile<TM, TN, BK, GRAD ? 0 : kConvChunk, POSMAJ>(lds, x, M, Wt, N, g, C, (int64_t)tile_m * (64 * TM), (int64_t)tile_n * (64 * TN), bias, res, relu, mask);
 }
 
 // 128x128 tiles with a 64x64 TAIL.  A launch whose tile count is a little above a whole number of rounds (1024 resident workgroups) ends
 // with a few 128x128 tiles running alone on their CUs at half the matrix-pipe rate while the other CUs idle -- 256->256 at 14x14, B = 1024:
 // 3136 tiles = 3 rounds + 64 tiles, 256 us of tail in a 1.79 ms launch.  Here the rows past the last whole round are cut into 64x64
 // tiles (a quarter of the work each, four times as many): the same blocks of the grid, same arithmetic per output element.
+// POSMAJ: the rows are virtual (m_split a multiple of 128: a 64-row tile is one half of a position's 128 images).
+template <bool POSMAJ>
 __global__ __launch_bounds__(256, kWgPerCu128) void conv3x3_tail_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N, Conv3x3Geom g,
                                                               float* __restrict__ C, TileMap tm_big, TileMap tm_small, int64_t m_split,
                                                               const float* __restrict__ bias, const float* __restrict__ res, int relu) {
@@ -55,22 +70,42 @@ __global__ __launch_bounds__(256, kWgPerCu128) void conv3x3_tail_kernel(const fl
     int tile_m, tile_n;
     if ((int)blockIdx.x < nbig) {
         tile_of_block(tm_big, tile_m, tile_n, (int)blockIdx.x, nbig);
-        conv3x3_tile<2, 2, 16>(lds, x, M, Wt, N, g, C, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, res, relu);
+        conv3x3_tile<2, 2, 16, kConvChunk, POSMAJ>(lds, x, M, Wt, N, g, C, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, res, relu);
     } else {
         tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        conv3x3_tile<1, 1, 32>(lds, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, res, relu);
+        conv3x3_tile<1, 1, 32, kConvChunk, POSMAJ>(lds, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, res, relu);
     }
 }
 
 // grad: the input-gradient instance (one chain over all 9 Cin terms, optional mask) -- chosen by the CALLER, not by the presence of a mask: a
 // gradient without a mask is the same sum as one with it
+// Mv > 0 (128x128 inference tiles only): position-major row order over Mv virtual rows (conv3x3_tile.hpp); the kernels still get the real M
 template <int TM, int TN, int BK>
 static void launch_conv3x3(const float* x, int64_t M, const float* w, int64_t N, const Conv3x3Geom& g, float* y, const float* bias,
-                           const float* res, int relu, hipStream_t st, const float* mask = nullptr, bool grad = false) {
+                           const float* res, int relu, hipStream_t st, const float* mask = nullptr, bool grad = false, int64_t Mv = 0) {
     TileMap tm;
     tm.m_active = nullptr;
     tm.tiles_m = (int)((M + 64 * TM - 1) / (64 * TM));
     tm.tiles_n = (int)((N + 64 * TN - 1) / (64 * TN));
+    if constexpr (TM == 2 && TN == 2) {
+        if (Mv > 0) {
+            tm.tiles_m = (int)(Mv / 128);
+            const int64_t vsplit = gemm_tail_split_rows(Mv, N, 256 * kWgPerCu128);
+            if (vsplit > 0) {
+                TileMap small;
+                small.m_active = nullptr;
+                tm.tiles_m = (int)(vsplit / 128);
+                small.tiles_m = (int)((Mv - vsplit) / 64);
+                small.tiles_n = (int)((N + 63) / 64);
+                hipLaunchKernelGGL(conv3x3_tail_kernel<true>, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, x, M, w, N, g,
+                                   y, tm, small, vsplit, bias, res, relu);
+                return;
+            }
+            hipLaunchKernelGGL((conv3x3_nhwc_kernel<2, 2, 16, false, true>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y, tm, bias,
+                               res, relu, mask);
+            return;
+        }
+    }
     const int64_t split = (TM == 2 && TN == 2 && !grad) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
     if (split > 0) {
         TileMap small;
@@ -78,7 +113,7 @@ static void launch_conv3x3(const float* x, int64_t M, const float* w, int64_t N,
         tm.tiles_m = (int)(split / 128);
         small.tiles_m = (int)((M - split + 63) / 64);
         small.tiles_n = (int)((N + 63) / 64);
-        hipLaunchKernelGGL(conv3x3_tail_kernel, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y,
+        hipLaunchKernelGGL(conv3x3_tail_kernel<false>, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y,
                            tm, small, split, bias, res, relu);
         return;
     }
@@ -259,6 +294,17 @@ static void launch_dual(const float* t, const float* x, int64_t M, const float* 
 }
 
 static std::atomic<int> g_force_conv_cfg{[] { const char* e = getenv("ISX_DEBUG_CONV_CFG"); return e ? atoi(e) : -1; }()};       // debug / A-B hook
+static std::atomic<int> g_pos_major{[] { const char* e = getenv("ISX_DEBUG_CONV_CFG"); return !(e && atoi(e) == 8); }()};     // 0: pixel-major row order everywhere (cfg 8)
+
+// Largest output map (Ho * Wo) that runs in the position-major row order (conv3x3_tile.hpp).  MEASURED, not assumed: the six 3x3 shapes of
+// ResNet-50 at B = 1024, both row orders alternating in one process (ms per launch, pixel-major -> position-major; share of the (pixel, tap)
+// pairs that is padding):
+//     512 @  7x7  stride 1   1.708 -> 1.496  (-12.4 %; padding 18.1 %)        512 @ 14x14 -> 7x7   stride 2   1.711 -> 1.595  (-6.8 %;  9.3 %)
+//     256 @ 14x14 stride 1   1.697 -> 1.592  (-6.2 %;  padding  9.3 %)        256 @ 28x28 -> 14x14 stride 2   1.696 -> 1.671  (-1.5 %;  4.7 %)
+//     128 @ 28x28 stride 1   1.752 -> 1.688  (-3.7 %;  padding  4.7 %)        128 @ 56x56 -> 28x28 stride 2   1.761 -> 1.723  (-2.2 %;  2.4 %)
+// Every shape gains, the 28x28 outputs included (their rows are 400 KB / 1.6 MB apart in x: no row-stride penalty showed), so the cut-off sits
+// at 28x28.  56x56 outputs (the Cin = 64 layers: 64x64 tiles or the fused expand kernel) have 1.2 % padding and stay pixel-major.
+constexpr int kPosMajorMaxP = 28 * 28;
 
 }  // namespace isx
 
@@ -302,11 +348,19 @@ ISX_API int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, c
     // 1.71 / 1.78 / 1.76; 64->64 at 56x56 - / 1.89 / 1.85): 128x128 (+ 64x64 tail) wherever the grid fills the chip, the shape with the
     // fewest idle CUs below that (512->512 at 14x14 with 64 images: 1568 tiles of 64x64 are 1.02 rounds, 784 of 128x64 are 0.77)
     static const float eff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
-    int best = pick_tile_cfg(M, N, gemm_tail_split_rows(M, N, 256 * kWgPerCu128), eff3x3, 0xD, kWgPerCu128);
+    // Position-major row order (conv3x3_tile.hpp: the k loop skips the padding taps) for the 128x128 tiles and their 64x64 tails:
+    // whole chunks of the two-level sum per tap, groups of 128 images that are not mostly empty, small maps, and 128 rows of x (H W Cin floats
+    // apart, plus the taps) / of y (P Cout floats apart) inside the 32-bit offsets of a buffer descriptor.  The tile model then sees the virtual rows.
+    const int64_t P = (int64_t)g.Ho * g.Wo;
+    const bool pos_major = g_pos_major && Cin % kConvChunk == 0 && B >= 128 && P <= kPosMajorMaxP &&
+                           (128ll * H * W + 2 * W + 4) * Cin * 4 < (1ll << 32) && 128ll * P * Cout * 4 < (1ll << 31);
+    const int64_t Mv = pos_major && ((B + 127) / 128 * P * 2) * ((N + 63) / 64) < (1ll << 31) ? (B + 127) / 128 * P * 128 : 0;        // (tile count of the virtual rows)
+    const int64_t Ms = Mv > 0 ? Mv : M;
+    int best = pick_tile_cfg(Ms, N, gemm_tail_split_rows(Ms, N, 256 * kWgPerCu128), eff3x3, 0xD, kWgPerCu128);
     { const int fc_ = g_force_conv_cfg; if (fc_ == 0 || fc_ == 2 || fc_ == 3) best = fc_; }
     hipStream_t st = (hipStream_t)stream;
     switch (best) {
-        case 0: launch_conv3x3<2, 2, 16>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st); break;
+        case 0: launch_conv3x3<2, 2, 16>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st, nullptr, false, Mv); break;
         case 2: launch_conv3x3<2, 1, 32>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st); break;
         default: launch_conv3x3<1, 1, 32>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st); break;
     }
@@ -375,6 +429,7 @@ ISX_API int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_
 // Test hook (include/isx.h): force the conv3x3 tile shape (0, 2, 3), -1 = automatic.
 ISX_API void isx_debug_set_conv_cfg(int c) {
     isx::g_tail_split = (c != 7);        // 7 = automatic tile choice WITHOUT the 64x64 tails (A/B)
-    g_force_conv_cfg = (c == 7) ? -1 : c;
+    isx::g_pos_major = (c != 8);         // 8 = automatic tile choice with the pixel-major row order on every 3x3 shape (A/B, tests)
+    g_force_conv_cfg = (c == 7 || c == 8) ? -1 : c;
 }
 

@@ -8,17 +8,51 @@ namespace isx {
 // Same tile machinery as cosine_gemm_kernel: M = B*Ho*Wo output pixels, N = Cout, K = 9*Cin ordered (kh, kw, ci),
 // weights pre-arranged (Cout, 3, 3, Cin).  A k-tile lies inside one filter tap (Cin % BK == 0), so the A rows of a
 // k-tile are the input pixels shifted by that tap: one base pixel per staged row, kept in registers, plus a
-// bounds test per tap (padding rows load zeros -- fma(0, w, acc) leaves acc unchanged, as skipping the tap would).
+// bounds test per tap (padding rows load zeros -- fma(0, w, acc) leaves acc unchanged, as skipping the tap would; the position-major
+// row order below does skip them).
 // Epilogue: bias (+ residual) + ReLU fused, wave-uniform row pointers.  Replaces conv2 of the torchvision
 // Bottleneck / both convolutions of BasicBlock inside the `features` trunk.
 struct Conv3x3Geom { int H, W, Cin, Ho, Wo, stride; };
+
+// ---- position-major row order (inference, small maps: isx_conv3x3_nhwc picks it, conv.hip) -------------------------------------------
+// In the pixel-major order a 128-row tile of a 7x7 map is 2.6 whole images: every tap is padding for SOME of its rows, so the padding
+// MFMAs cannot be skipped -- 18.1 % of the (pixel, tap) pairs at 7x7 stride 1, 9.3 % at 14x14.  Here the output rows are numbered
+//     v = ((grp * P + p) * 128 + i)        P = Ho * Wo, p = ho * Wo + wo, image b = 128 grp + i
+// so a 128-row tile (and each 64-row tail tile) is ONE output position p of up to 128 images.  Tap validity is then one scalar per tile,
+// and the k loop visits the valid taps only: a skipped tap costs no loads, no LDS stores, no barriers and no MFMAs.  The visited taps keep
+// the (kh, kw, ci) order.  The image group is outermost: neighbouring tiles are neighbouring positions of the same images, which share taps
+// in their XCD's L2.
+// Same bits as the pixel-major order: Cin % kConvChunk == 0 is required, so a tap is a whole number of chunks of the two-level sum.  A
+// padding chunk's chain is fma(0, w, +0) = +0 for every FINITE w, and tot -- which starts at +0 and can therefore never be -0 -- is
+// unchanged by tot + (+0).  A NON-FINITE weight under a padding tap gives NaN in the pixel-major order (0 * inf) and is skipped here: the
+// two orders agree on finite weights only (the oracle's tests use no others).
+// Rows of a tile are H W Cin floats apart in x and P Cout floats apart in y: isx_conv3x3_nhwc admits the order only where 128 such rows
+// stay inside the 32-bit offsets of a buffer descriptor.  Rows with b >= B load image B - 1 again and are not stored.
+struct PosMajorTile { int B, b0, p, hi0, wi0, kh_lo, kh_n, kw_lo, kw_n; };
+__device__ __forceinline__ PosMajorTile pos_major_tile(const Conv3x3Geom& g, int64_t M, int64_t m0) {
+    PosMajorTile t;
+    const int P = g.Ho * g.Wo, q = (int)(m0 >> 7), grp = q / P;
+    t.B = (int)(M / P);
+    t.p = q - grp * P;
+    t.b0 = grp * 128 + (int)(m0 & 127);
+    const int ho = t.p / g.Wo, wo = t.p - ho * g.Wo;
+    t.hi0 = ho * g.stride - 1;
+    t.wi0 = wo * g.stride - 1;
+    const int kh_hi = g.H - 1 - t.hi0 < 2 ? g.H - 1 - t.hi0 : 2, kw_hi = g.W - 1 - t.wi0 < 2 ? g.W - 1 - t.wi0 : 2;
+    t.kh_lo = t.hi0 < 0 ? 1 : 0;
+    t.kw_lo = t.wi0 < 0 ? 1 : 0;
+    t.kh_n = kh_hi - t.kh_lo + 1;
+    t.kw_n = kw_hi - t.kw_lo + 1;
+    return t;
+}
 
 // accumulators of one (64 TM) x (64 TN) output tile at rows m0.., columns n0.. (every wave has left the LDS when this returns);
 // lds: BK * (64 TM + 64 TN + 2 pads) floats
 // AHEAD2 (64x64 tiles only): operands requested two k-tiles ahead instead of one (16 more VGPRs: the fused expand kernel has them, the plain
 // 64x64 kernel at six workgroups per CU does not).
 // CHUNK: terms per first-level chain of the two-level sum (gemm_tile.hpp; the inference trunk), 0 = one chain over all 9 Cin terms (gradients)
-template <int TM, int TN, int BK, bool AHEAD2 = false, int CHUNK = kConvChunk>
+// POSMAJ: position-major row order (see the block above PosMajorTile); m0 is then a VIRTUAL row, M stays the real row count B * Ho * Wo
+template <int TM, int TN, int BK, bool AHEAD2 = false, int CHUNK = kConvChunk, bool POSMAJ = false>
 __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N,
                                                  const Conv3x3Geom& g, int64_t m0, int64_t n0, f32x16 (&acc)[TM][TN]) {
     constexpr int BM = 64 * TM, BN = 64 * TN, LDA = BM + lds_pad(BK), LDB = BN + lds_pad(BK);
@@ -26,6 +60,7 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     float* As = lds;
     float* Bs = lds + BK * LDA;
     const int D = 9 * g.Cin;
+    static_assert(!POSMAJ || (!AHEAD2 && CHUNK != 0), "position-major rows: the plain staged loop of the inference kernels only");
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / 2, wn = wave % 2;
@@ -42,20 +77,28 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
 
     // staged A rows of this thread: top-left input pixel of the 3x3 window (may be -1: padding)
     int pbase[NA], hw0[NA];                       // pixel index of (hi0, wi0); (hi0 + 1) << 16 | (wi0 + 1)
+    const PosMajorTile pt = POSMAJ ? pos_major_tile(g, M, m0) : PosMajorTile{};
+    const int kh_lo = POSMAJ ? pt.kh_lo : 0, kh_n = POSMAJ ? pt.kh_n : 3, kw_lo = POSMAJ ? pt.kw_lo : 0, kw_n = POSMAJ ? pt.kw_n : 3;    // taps the k loop visits
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
         const int idx = j * 256 + threadIdx.x;
-        int64_t m = m0 + idx / CH;
-        m = m < M ? m : M - 1;
-        const int hw = g.Ho * g.Wo;
-        const int b = (int)(m / hw), rem = (int)(m - (int64_t)b * hw);
-        const int ho = rem / g.Wo, wo = rem - ho * g.Wo;
-        const int hi0 = ho * g.stride - 1, wi0 = wo * g.stride - 1;
-        pbase[j] = (b * g.H + hi0) * g.W + wi0;
-        hw0[j] = ((hi0 + 1) << 16) | (wi0 + 1);
+        if constexpr (POSMAJ) {                   // one output position, image b0 + row (images past the batch repeat the last one: never stored)
+            const int b = pt.b0 + idx / CH < pt.B ? pt.b0 + idx / CH : pt.B - 1;
+            pbase[j] = (b * g.H + pt.hi0) * g.W + pt.wi0;
+            hw0[j] = 0;
+        } else {
+            int64_t m = m0 + idx / CH;
+            m = m < M ? m : M - 1;
+            const int hw = g.Ho * g.Wo;
+            const int b = (int)(m / hw), rem = (int)(m - (int64_t)b * hw);
+            const int ho = rem / g.Wo, wo = rem - ho * g.Wo;
+            const int hi0 = ho * g.stride - 1, wi0 = wo * g.stride - 1;
+            pbase[j] = (b * g.H + hi0) * g.W + wi0;
+            hw0[j] = ((hi0 + 1) << 16) | (wi0 + 1);
+        }
     }
     const int c4 = (threadIdx.x % CH) << 2;
-    int kh = 0, kw = 0, ci0 = 0;                  // tap / channel offset of the NEXT k-tile to load (uniform)
+    int kh = kh_lo, kw = kw_lo, ci0 = 0;          // tap / channel offset of the NEXT k-tile to load (uniform)
     float4 ra[NA], rb[BN * BK / 1024];
     // A rows come through BUFFER loads: a wave-uniform descriptor that starts at the first input pixel this tile can touch, one 32-bit
     // byte offset per staged row (recomputed once per filter tap), the channel offset inside the tap as the SGPR offset.  A padding
@@ -65,12 +108,20 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     const int bf = (int)(mf / hw_), remf = (int)(mf - (int64_t)bf * hw_);
     const int hof = remf / g.Wo, wof = remf - hof * g.Wo;
     int64_t base_pix = ((int64_t)bf * g.H + (hof * g.stride - 1)) * g.W + (wof * g.stride - 1);      // top-left tap of the tile's first row
+    if constexpr (POSMAJ) {                       // the first visited tap of the tile's first image: no visited tap of any row lies below it
+        const int bl = pt.b0 < pt.B ? pt.b0 : pt.B - 1;
+        base_pix = ((int64_t)bl * g.H + pt.hi0 + kh_lo) * g.W + pt.wi0 + kw_lo;
+    }
     base_pix = base_pix > 0 ? base_pix : 0;
     const int64_t left = ((int64_t)(M / hw_) * g.H * g.W - base_pix) * g.Cin * 4;                     // bytes up to the end of the input
     const auto xr = uniform_rsrc(x + base_pix * g.Cin, left);
     unsigned voff[NA];                            // byte offset of the current tap's pixel of each staged row (0xFFFFFFFF: padding)
+    if constexpr (POSMAJ) {                       // every visited tap is valid for every row: the row offsets are loop invariant, the tap moves in the SGPR offset
+#pragma unroll
+        for (int j = 0; j < NA; ++j) voff[j] = (unsigned)(((int64_t)pbase[j] + kh_lo * g.W + kw_lo - base_pix) * g.Cin + c4) * 4u;
+    }
     auto load_a = [&]() {
-        if (ci0 == 0) {                           // new tap (uniform branch, once per Cin / BK k-tiles)
+        if (!POSMAJ && ci0 == 0) {                // new tap (uniform branch, once per Cin / BK k-tiles)
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
                 const int hi = (hw0[j] >> 16) - 1 + kh, wi = (hw0[j] & 0xFFFF) - 1 + kw;
@@ -78,16 +129,18 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
                 voff[j] = ok ? (unsigned)(((int64_t)pbase[j] + kh * g.W + kw - base_pix) * g.Cin + c4) * 4u : 0xFFFFFFFFu;
             }
         }
-        const unsigned soff = (unsigned)ci0 * 4u;
+        const unsigned soff = (unsigned)((POSMAJ ? ((kh - kh_lo) * g.W + (kw - kw_lo)) * g.Cin : 0) + ci0) * 4u;
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
             // (bit_cast of the whole vector: indexing the builtin's result through `auto` gave element 0 four times with hipcc 7.2)
             ra[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, voff[j], soff, 0));
         }
         ci0 += BK;
-        if (ci0 == g.Cin) { ci0 = 0; if (++kw == 3) { kw = 0; ++kh; } }
+        if (ci0 == g.Cin) { ci0 = 0; if (++kw == kw_lo + kw_n) { kw = kw_lo; ++kh; } }
     };
-    const int nk = D / BK;
+    // POSMAJ: k offset of the NEXT k-tile in the weight rows -- the visited taps keep their (kh, kw, ci) place in the 9 Cin terms
+    auto next_k0 = [&]() { return (kh * 3 + kw) * g.Cin + ci0; };
+    const int nk = POSMAJ ? kh_n * kw_n * (g.Cin / BK) : D / BK;
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
     constexpr bool PINNED = CHUNK != 0 && TM * TN == 4;
@@ -147,7 +200,7 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
         return;
     }
     load_a();
-    load_tile<true, BN, BK>(Wt, N, D, n0, 0, rb);
+    load_tile<true, BN, BK>(Wt, N, D, n0, POSMAJ ? (kh_lo * 3 + kw_lo) * g.Cin : 0, rb);       // (the first visited tap)
     store_tile<BM, BK>(As, ra);
     store_tile<BN, BK>(Bs, rb);
     __syncthreads();
@@ -159,8 +212,9 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     auto body = [&](int kt, auto zero_c) {
         const bool more = (kt + 1 < nk);
         if (more) {
+            const int k0 = POSMAJ ? next_k0() : 0;           // (before load_a moves on)
             load_a();
-            load_tile<true, BN, BK>(Wt, N, D, n0, (kt + 1) * BK, rb);
+            load_tile<true, BN, BK>(Wt, N, D, n0, POSMAJ ? k0 : (kt + 1) * BK, rb);
         }
         mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
         __syncthreads();
