@@ -325,7 +325,9 @@ int isx_comm_allgather_rows(void* comm, const float* rows_local, int64_t rows, i
 /* train/siamese_descriptor.py:94-128 (and siamese_regions.py:94-135): for every positive couple
  * (i1[c], i2[c]) the negative = arg-max over j of sim[i1][j] after excluding same-label items and, in
  * the semi-hard phase (epoch < train_epoch_switch), items with sim >= sim[i1][i2]; ties -> smallest
- * index; neg[c] = -1 when everything is excluded (caller picks a random negative).
+ * index, -0 and +0 being a tie; neg[c] = -1 when everything is excluded (caller picks a random negative).
+ * Excluded items take no part in the arg-max (the reference fills them with -2: the same for every score
+ * above -2); NaN scores are undefined, as in the reference.
  * sim: (N,N); labels: (N) int32; i1, i2, neg: (n_couples) int64. */
 int isx_mine_negatives(const float* sim, int64_t N, const int32_t* labels, const int64_t* i1, const int64_t* i2,
                        int64_t n_couples, int semi_hard, int64_t* neg, isx_stream_t stream);
@@ -338,15 +340,20 @@ int isx_mine_negatives_rows(const float* sim_rows, int64_t N, int64_t row_base, 
 
 /* model/custom_modules.py:153-171 TripletLossFun.forward, per-row part: loss_rows[b] = max(0, l_b) with
  * l_b = a.n - a.p + margin (normalized) or (|a-p|^2 - |a-n|^2 + 2 margin)/2.  The caller sums the rows
- * (and divides by B for size_average).  anchor, pos, neg: (B,D). */
+ * (and divides by B for size_average).  anchor, pos, neg: (B,D).  One wave per row: lane i adds its terms
+ * j = i, i + 64, ... in ascending order from +0 -- a term is the unfused a*n - a*p, resp. dp*dp - dn*dn with
+ * dp = a - p, dn = a - n -- the 64 lane sums meet in a butterfly (xor 32, 16, 8, 4, 2, 1), then s + margin,
+ * resp. (s + 2 margin) * 0.5.  A row's value does not depend on the rows around it. */
 int isx_triplet_loss_fwd(const float* anchor, const float* pos, const float* neg, int64_t B, int D, float margin,
                          int normalized, float* loss_rows, isx_stream_t stream);
 
 /* model/custom_modules.py:173-203 TripletLossFun.backward: g_a = n - p, g_p = -a (p - a), g_n = a (a - n)
- * on rows with loss_rows > 0, zero elsewhere, times `scale`. */
+ * on rows with loss_rows > 0, +0 elsewhere (loss_rows of -0 or +0 included), each element times `scale`
+ * in ONE multiply. */
 int isx_triplet_loss_bwd(const float* anchor, const float* pos, const float* neg, const float* loss_rows, int64_t B, int D,
                          float scale, int normalized, float* g_anchor, float* g_pos, float* g_neg, isx_stream_t stream);
-/* The same with the incoming gradient as a device scalar: gradients times scale * scale_dev[0] (no host read-back of grad_output). */
+/* The same with the incoming gradient as a device scalar: gradients times fl(scale * scale_dev[0]), the product formed first (no host
+ * read-back of grad_output). */
 int isx_triplet_loss_bwd_dev(const float* anchor, const float* pos, const float* neg, const float* loss_rows, int64_t B, int D,
                              float scale, const float* scale_dev, int normalized, float* g_anchor, float* g_pos, float* g_neg,
                              isx_stream_t stream);

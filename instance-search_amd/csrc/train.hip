@@ -8,9 +8,10 @@ namespace isx {
 
 // One 256-thread workgroup per positive couple (i1, i2): the negative is the most similar gallery
 // item of anchor i1 that does not share its label and (semi-hard phase, FaceNet) is strictly less
-// similar than the positive.  Excluded entries are treated as -2 exactly like the reference
-// (`sims[ind_exl] = -2; sims.max(0)`), ties go to the smallest index; -1 = every item excluded
-// (the caller falls back to a random negative, reference :100-107,129-131).
+// similar than the positive (an item with s == sim_pos is excluded: `>=`, an IEEE compare).  Excluded entries take no part in the
+// arg-max; the reference fills them with -2 (`sims[ind_exl] = -2; sims.max(0)`), the same answer for every score above -2, which
+// every cosine is.  The order is (score with -0 folded onto +0, then smallest index); -1 = every item excluded (the caller falls
+// back to a random negative, reference :100-107,129-131).  NaN scores: undefined, as in the reference.
 // sim holds rows [row_base, row_base + rows) of the N x N matrix (row_base = 0, rows = N: the whole matrix).
 __global__ __launch_bounds__(256) void mine_negatives_kernel(const float* __restrict__ sim, int64_t N, int64_t row_base,
                                                              const int32_t* __restrict__ lab, const int64_t* __restrict__ i1,
@@ -40,7 +41,10 @@ __global__ __launch_bounds__(256) void mine_negatives_kernel(const float* __rest
 }
 
 // One wave per triplet row.  normalized: l = a.n - a.p + margin ; else l = (|a-p|^2 - |a-n|^2 + 2 margin) / 2;
-// loss_rows[b] = max(l, 0)  (the reference zeroes l <= 0, custom_modules.py:166-167).
+// loss_rows[b] = l > 0 ? l : +0  (the reference zeroes l <= 0, custom_modules.py:166-167).
+// The sum (tests/_triplet_model.py pins it): lane i adds its terms j = i, i + 64, ... in ascending order from +0, a term being the unfused
+// a*n - a*p, resp. dp*dp - dn*dn with dp = a - p, dn = a - n; the 64 lane sums meet in the butterfly xor 32, 16, 8, 4, 2, 1; then
+// s + margin, resp. (s + 2 margin) * 0.5.
 __global__ __launch_bounds__(256) void triplet_fwd_kernel(const float* __restrict__ A, const float* __restrict__ P,
                                                           const float* __restrict__ Ng, int64_t B, int D, float margin,
                                                           int normalized, float* __restrict__ loss_rows) {

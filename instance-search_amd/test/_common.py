@@ -386,6 +386,9 @@ def run_cli(argv, usage, spec, required, main, P):
             dist.init_process_group('nccl', device_id=torch.device('cuda', device))
         else:
             dist.init_process_group('gloo')
+            # gloo writes "[Gloo] Rank r is connected to ..." to the stdout the ranks share, in pieces, when a rank's mesh is up: nobody prints a
+            # result line before every rank is past that point, or a late rank's chatter lands inside rank 0's lines
+            dist.barrier()
         if dist.get_rank() != 0:
             quiet = open(os.devnull, 'w')
     try:
