@@ -64,17 +64,10 @@ template <bool POSMAJ>
 __global__ __launch_bounds__(256, kWgPerCu128) void conv3x3_tail_kernel(const float* __restrict__ x, int64_t M, const float* __restrict__ Wt, int64_t N, Conv3x3Geom g,
                                                               float* __restrict__ C, TileMap tm_big, TileMap tm_small, int64_t m_split,
                                                               const float* __restrict__ bias, const float* __restrict__ res, int relu) {
-    constexpr int kBig = 16 * (128 + 128 + 2 * lds_pad(16));
-    __shared__ float lds[kBig > kTailLdsFloats ? kBig : kTailLdsFloats];
-    const int nbig = tm_big.tiles_m * tm_big.tiles_n;                                // a multiple of 8: the XCD of a block is the same in both numberings
-    int tile_m, tile_n;
-    if ((int)blockIdx.x < nbig) {
-        tile_of_block(tm_big, tile_m, tile_n, (int)blockIdx.x, nbig);
-        conv3x3_tile<2, 2, 16, kConvChunk, POSMAJ>(lds, x, M, Wt, N, g, C, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, res, relu);
-    } else {
-        tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        conv3x3_tile<1, 1, 32, kConvChunk, POSMAJ>(lds, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, res, relu);
-    }
+    __shared__ float lds[kTailKernelLdsFloats];
+    tail_tile_of_block(tm_big, tm_small, m_split, [&](auto T, auto BK, int64_t m0, int64_t n0) {
+        conv3x3_tile<T(), T(), BK(), kConvChunk, POSMAJ>(lds, x, M, Wt, N, g, C, m0, n0, bias, res, relu);
+    });
 }
 
 // grad: the input-gradient instance (one chain over all 9 Cin terms, optional mask) -- chosen by the CALLER, not by the presence of a mask: a
@@ -88,34 +81,20 @@ static void launch_conv3x3(const float* x, int64_t M, const float* w, int64_t N,
     tm.tiles_m = (int)((M + 64 * TM - 1) / (64 * TM));
     tm.tiles_n = (int)((N + 64 * TN - 1) / (64 * TN));
     if constexpr (TM == 2 && TN == 2) {
+        const int64_t rows = Mv > 0 ? Mv : M;
+        const int64_t split = grad ? 0 : gemm_tail_split_rows(rows, N, 256 * kWgPerCu128);
+        if (split > 0) {
+            const TailGrid tg = gemm_tail_grid(rows, N, split);
+            if (Mv > 0) hipLaunchKernelGGL(conv3x3_tail_kernel<true>, dim3(tg.blocks), dim3(256), 0, st, x, M, w, N, g, y, tg.big, tg.small, split, bias, res, relu);
+            else hipLaunchKernelGGL(conv3x3_tail_kernel<false>, dim3(tg.blocks), dim3(256), 0, st, x, M, w, N, g, y, tg.big, tg.small, split, bias, res, relu);
+            return;
+        }
         if (Mv > 0) {
             tm.tiles_m = (int)(Mv / 128);
-            const int64_t vsplit = gemm_tail_split_rows(Mv, N, 256 * kWgPerCu128);
-            if (vsplit > 0) {
-                TileMap small;
-                small.m_active = nullptr;
-                tm.tiles_m = (int)(vsplit / 128);
-                small.tiles_m = (int)((Mv - vsplit) / 64);
-                small.tiles_n = (int)((N + 63) / 64);
-                hipLaunchKernelGGL(conv3x3_tail_kernel<true>, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, x, M, w, N, g,
-                                   y, tm, small, vsplit, bias, res, relu);
-                return;
-            }
             hipLaunchKernelGGL((conv3x3_nhwc_kernel<2, 2, 16, false, true>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y, tm, bias,
                                res, relu, mask);
             return;
         }
-    }
-    const int64_t split = (TM == 2 && TN == 2 && !grad) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
-    if (split > 0) {
-        TileMap small;
-        small.m_active = nullptr;
-        tm.tiles_m = (int)(split / 128);
-        small.tiles_m = (int)((M - split + 63) / 64);
-        small.tiles_n = (int)((N + 63) / 64);
-        hipLaunchKernelGGL(conv3x3_tail_kernel<false>, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y,
-                           tm, small, split, bias, res, relu);
-        return;
     }
     if (grad) hipLaunchKernelGGL((conv3x3_nhwc_kernel<TM, TN, BK, true>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, x, M, w, N, g, y, tm, bias,
                                  res, relu, mask);
@@ -198,46 +177,18 @@ __device__ __forceinline__ void conv1x1_dual_tile(float* __restrict__ lds, const
     store_tile<BN, BK>(Bs, rb);
     __syncthreads();
 
+    // the flattened [t ; x] reduction in chunks of the two-level sum
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = kConvChunk != 0 && TM * TN == 4;
-    KtilePtrs<BK> pins;
-    if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
-    // outer loop: chunks of the two-level sum over the flattened [t ; x] reduction; inner loop: the staged k-tiles of a chunk (gemm_tile.hpp); the
-    // first k-tile of a chunk starts its chains with C = 0
-    f32x16 (*totp)[TN] = nullptr;
-    if constexpr (kConvChunk != 0) totp = tot;
-    auto body = [&](int kt, auto zero_c) {
-        const bool more = (kt + 1 < nk);
-        if (more) {
+    staged_kloop<TM, TN, BK, kConvChunk>(a_base, b_base, nk, acc, tot,
+        [&](int kt) {
             load_a();
-            load_tile<true, BN, BK>(Wt, N, D, n0, (kt + 1) * BK, rb);
-        }
-        mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
-        __syncthreads();
-        if (more) {
+            load_tile<true, BN, BK>(Wt, N, D, n0, kt * BK, rb);
+        },
+        [&]() {
             store_tile<BM, BK>(As, ra);
             store_tile<BN, BK>(Bs, rb);
-            __syncthreads();
-        }
-    };
-    if constexpr (kConvChunk == 0) {
-        for (int kt = 0; kt < nk; ++kt) body(kt, std::false_type());
-    } else {
-        for (int kt = 0; kt < nk;) {
-            const int kend = kt + kConvChunk / BK < nk ? kt + kConvChunk / BK : nk;
-            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
-            for (; kt < kend; ++kt) body(kt, std::false_type());
-            if (!PINNED) add_chunk<TM, TN>(tot, acc);
-        }
-        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
-    }
-    if constexpr (kConvChunk != 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
-    }
+        });
 
     const int wm_u = __builtin_amdgcn_readfirstlane(wm), wn_u = __builtin_amdgcn_readfirstlane(wn);
     conv_epilogue_buffers<TM, TN>(acc, C, nullptr, bias, relu, m0, M, n0, N, ldc, BM, wm_u * (32 * TM), wn_u * (32 * TN), l31, half);
@@ -258,17 +209,10 @@ __global__ __launch_bounds__(256, TM * TN == 1 ? 6 : TM * TN == 4 ? kWgPerCu128 
 __global__ __launch_bounds__(256, kWgPerCu128) void conv1x1_dual_tail_kernel(const float* __restrict__ t, const float* __restrict__ x, int64_t M, const float* __restrict__ Wt,
                                                                    int64_t N, DualGeom g, float* __restrict__ C, TileMap tm_big, TileMap tm_small,
                                                                    int64_t m_split, const float* __restrict__ bias, int relu) {
-    constexpr int kBig = 16 * (128 + 128 + 2 * lds_pad(16));
-    __shared__ float lds[kBig > kTailLdsFloats ? kBig : kTailLdsFloats];
-    const int nbig = tm_big.tiles_m * tm_big.tiles_n;
-    int tile_m, tile_n;
-    if ((int)blockIdx.x < nbig) {
-        tile_of_block(tm_big, tile_m, tile_n, (int)blockIdx.x, nbig);
-        conv1x1_dual_tile<2, 2, 16>(lds, t, x, M, Wt, N, g, C, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, relu);
-    } else {
-        tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        conv1x1_dual_tile<1, 1, 32>(lds, t, x, M, Wt, N, g, C, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, relu);
-    }
+    __shared__ float lds[kTailKernelLdsFloats];
+    tail_tile_of_block(tm_big, tm_small, m_split, [&](auto T, auto BK, int64_t m0, int64_t n0) {
+        conv1x1_dual_tile<T(), T(), BK()>(lds, t, x, M, Wt, N, g, C, m0, n0, bias, relu);
+    });
 }
 
 template <int TM, int TN, int BK>
@@ -280,13 +224,8 @@ static void launch_dual(const float* t, const float* x, int64_t M, const float* 
     tm.tiles_n = (int)((N + 64 * TN - 1) / (64 * TN));
     const int64_t split = (TM == 2 && TN == 2) ? gemm_tail_split_rows(M, N, 256 * kWgPerCu128) : 0;
     if (split > 0) {
-        TileMap small;
-        small.m_active = nullptr;
-        tm.tiles_m = (int)(split / 128);
-        small.tiles_m = (int)((M - split + 63) / 64);
-        small.tiles_n = (int)((N + 63) / 64);
-        hipLaunchKernelGGL(conv1x1_dual_tail_kernel, dim3((unsigned)(tm.tiles_m * tm.tiles_n + small.tiles_m * small.tiles_n)), dim3(256), 0, st, t, x, M, w, N, g,
-                           y, tm, small, split, bias, relu);
+        const TailGrid tg = gemm_tail_grid(M, N, split);
+        hipLaunchKernelGGL(conv1x1_dual_tail_kernel, dim3(tg.blocks), dim3(256), 0, st, t, x, M, w, N, g, y, tg.big, tg.small, split, bias, relu);
         return;
     }
     hipLaunchKernelGGL((conv1x1_dual_nhwc_kernel<TM, TN, BK>), dim3((unsigned)(tm.tiles_m * tm.tiles_n)), dim3(256), 0, st, t, x, M, w, N, g, y, tm,
@@ -305,6 +244,9 @@ static std::atomic<int> g_pos_major{[] { const char* e = getenv("ISX_DEBUG_CONV_
 // Every shape gains, the 28x28 outputs included (their rows are 400 KB / 1.6 MB apart in x: no row-stride penalty showed), so the cut-off sits
 // at 28x28.  56x56 outputs (the Cin = 64 layers: 64x64 tiles or the fused expand kernel) have 1.2 % padding and stay pixel-major.
 constexpr int kPosMajorMaxP = 28 * 28;
+
+// steady-state efficiency of the 3x3 tile shapes (128x128, -, 128x64, 64x64) for pick_tile_cfg: forward and input gradient
+static const float kEff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
 
 }  // namespace isx
 
@@ -347,7 +289,6 @@ ISX_API int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, c
     // the round / tail model of the GEMMs with this kernel's efficiencies (B = 1024, ms for 128x128 / 128x64 / 64x64: 128->128 at 28x28
     // 1.71 / 1.78 / 1.76; 64->64 at 56x56 - / 1.89 / 1.85): 128x128 (+ 64x64 tail) wherever the grid fills the chip, the shape with the
     // fewest idle CUs below that (512->512 at 14x14 with 64 images: 1568 tiles of 64x64 are 1.02 rounds, 784 of 128x64 are 0.77)
-    static const float eff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
     // Position-major row order (conv3x3_tile.hpp: the k loop skips the padding taps) for the 128x128 tiles and their 64x64 tails:
     // whole chunks of the two-level sum per tap, groups of 128 images that are not mostly empty, small maps, and 128 rows of x (H W Cin floats
     // apart, plus the taps) / of y (P Cout floats apart) inside the 32-bit offsets of a buffer descriptor.  The tile model then sees the virtual rows.
@@ -356,14 +297,12 @@ ISX_API int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, c
                            (128ll * H * W + 2 * W + 4) * Cin * 4 < (1ll << 32) && 128ll * P * Cout * 4 < (1ll << 31);
     const int64_t Mv = pos_major && ((B + 127) / 128 * P * 2) * ((N + 63) / 64) < (1ll << 31) ? (B + 127) / 128 * P * 128 : 0;        // (tile count of the virtual rows)
     const int64_t Ms = Mv > 0 ? Mv : M;
-    int best = pick_tile_cfg(Ms, N, gemm_tail_split_rows(Ms, N, 256 * kWgPerCu128), eff3x3, 0xD, kWgPerCu128);
+    int best = pick_tile_cfg(Ms, N, gemm_tail_split_rows(Ms, N, 256 * kWgPerCu128), kEff3x3, 0xD, kWgPerCu128);
     { const int fc_ = g_force_conv_cfg; if (fc_ == 0 || fc_ == 2 || fc_ == 3) best = fc_; }
     hipStream_t st = (hipStream_t)stream;
-    switch (best) {
-        case 0: launch_conv3x3<2, 2, 16>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st, nullptr, false, Mv); break;
-        case 2: launch_conv3x3<2, 1, 32>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st); break;
-        default: launch_conv3x3<1, 1, 32>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st); break;
-    }
+    with_tile_shape<0xD>(best, [&](auto TM, auto TN, auto BK) {          // (Mv: the 128x128 shape only)
+        launch_conv3x3<TM(), TN(), BK()>(x, M, w_ohwi, N, g, y, bias, residual, relu ? 1 : 0, st, nullptr, false, Mv);
+    });
     ISX_CHECK_LAUNCH("isx_conv3x3_nhwc");
     return ISX_OK;
 }
@@ -383,14 +322,11 @@ ISX_API int isx_conv3x3_dgrad_nhwc(const float* dz, int64_t B, int H, int W, int
     Conv3x3Geom g;
     g.H = H; g.W = W; g.Cin = Cout; g.stride = 1; g.Ho = H; g.Wo = W;
     const int64_t M = B * H * W, N = Cin;
-    static const float eff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
-    const int best = pick_tile_cfg(M, N, 0, eff3x3, 0xD);
+    const int best = pick_tile_cfg(M, N, 0, kEff3x3, 0xD);
     hipStream_t st = (hipStream_t)stream;
-    switch (best) {
-        case 0: launch_conv3x3<2, 2, 16>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true); break;
-        case 2: launch_conv3x3<2, 1, 32>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true); break;
-        default: launch_conv3x3<1, 1, 32>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true); break;
-    }
+    with_tile_shape<0xD>(best, [&](auto TM, auto TN, auto BK) {
+        launch_conv3x3<TM(), TN(), BK()>(dz, M, wt, N, g, dx, nullptr, nullptr, 0, st, mask, true);
+    });
     ISX_CHECK_LAUNCH("isx_conv3x3_dgrad_nhwc");
     return ISX_OK;
 }
@@ -419,9 +355,9 @@ ISX_API int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_
     int best = pick_tile_cfg(M, N, gemm_tail_split_rows(M, N, 256 * kWgPerCu128), eff_dual, 0xD, kWgPerCu128);
     { const int fc_ = g_force_conv_cfg; if (fc_ == 0 || fc_ == 2 || fc_ == 3) best = fc_; }
     hipStream_t st = (hipStream_t)stream;
-    if (best == 0) launch_dual<2, 2, 16>(t, x, M, w_cat, N, g, y, bias, relu ? 1 : 0, st);
-    else if (best == 2) launch_dual<2, 1, 32>(t, x, M, w_cat, N, g, y, bias, relu ? 1 : 0, st);
-    else launch_dual<1, 1, 32>(t, x, M, w_cat, N, g, y, bias, relu ? 1 : 0, st);
+    with_tile_shape<0xD>(best, [&](auto TM, auto TN, auto BK) {
+        launch_dual<TM(), TN(), BK()>(t, x, M, w_cat, N, g, y, bias, relu ? 1 : 0, st);
+    });
     ISX_CHECK_LAUNCH("isx_conv1x1_dual_nhwc");
     return ISX_OK;
 }

@@ -143,17 +143,6 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     const int nk = POSMAJ ? kh_n * kw_n * (g.Cin / BK) : D / BK;
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4;
-    KtilePtrs<BK> pins;
-    if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
-    auto take_tot = [&]() {                       // the tile's value: the sum of the chunk sums
-        if constexpr (CHUNK != 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
-        }
-    };
     if (AHEAD2 && TM * TN == 1 && !(nk & 1)) {
         // 64x64 tiles: a k-tile is 16 MFMAs per wave -- 1024 matrix-pipe cycles, ~4000 when four waves share the SIMD -- while a loaded HBM / L2
         // round trip can take longer (scratch/lab/expand_lab.hip: 6200 -> 5800 cycles per k-tile, fused kernel 2.98 -> 2.95 ms): the operands are
@@ -196,7 +185,7 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
             if constexpr (CHUNK == 2 * BK) add_chunk<TM, TN>(tot, acc);
             else if constexpr (CHUNK != 0) { if (((kt + 2) * BK) % CHUNK == 0 || kt + 2 >= nk) add_chunk<TM, TN>(tot, acc); }
         }
-        take_tot();
+        if constexpr (CHUNK != 0) acc[0][0] = tot[0][0];       // the tile's value: the sum of the chunk sums
         return;
     }
     load_a();
@@ -205,37 +194,16 @@ __device__ __forceinline__ void conv3x3_mainloop(float* __restrict__ lds, const 
     store_tile<BN, BK>(Bs, rb);
     __syncthreads();
 
-    // outer loop: chunks of the two-level sum (one pass when CHUNK == 0); inner loop: the staged k-tiles of a chunk (gemm_tile.hpp); the first
-    // k-tile of a chunk starts its chains with C = 0
-    f32x16 (*totp)[TN] = nullptr;
-    if constexpr (CHUNK != 0) totp = tot;
-    auto body = [&](int kt, auto zero_c) {
-        const bool more = (kt + 1 < nk);
-        if (more) {
+    staged_kloop<TM, TN, BK, CHUNK>(a_base, b_base, nk, acc, tot,
+        [&](int kt) {
             const int k0 = POSMAJ ? next_k0() : 0;           // (before load_a moves on)
             load_a();
-            load_tile<true, BN, BK>(Wt, N, D, n0, POSMAJ ? k0 : (kt + 1) * BK, rb);
-        }
-        mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
-        __syncthreads();
-        if (more) {
+            load_tile<true, BN, BK>(Wt, N, D, n0, POSMAJ ? k0 : kt * BK, rb);
+        },
+        [&]() {
             store_tile<BM, BK>(As, ra);
             store_tile<BN, BK>(Bs, rb);
-            __syncthreads();
-        }
-    };
-    if constexpr (CHUNK == 0) {
-        for (int kt = 0; kt < nk; ++kt) body(kt, std::false_type());
-    } else {
-        for (int kt = 0; kt < nk;) {
-            const int kend = kt + CHUNK / BK < nk ? kt + CHUNK / BK : nk;
-            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
-            for (; kt < kend; ++kt) body(kt, std::false_type());
-            if (!PINNED) add_chunk<TM, TN>(tot, acc);
-        }
-        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
-    }
-    take_tot();
+        });
 }
 
 }  // namespace isx

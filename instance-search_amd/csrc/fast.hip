@@ -36,7 +36,7 @@
 #include <hip/hip_fp16.h>
 #include <type_traits>
 
-#include "isx_internal.hpp"
+#include "gemm_tile.hpp"
 
 namespace isx {
 
@@ -195,11 +195,9 @@ __global__ __launch_bounds__(256) void cosine_gemm_f16_kernel(const _Float16* __
     char* As = lds;
     char* Bs = lds + HTILE_B;
     // XCD-aware bijective remap + 16-wide n groups (as the fp32 kernel)
-    const int nwg = tiles_m * tiles_n;
-    const int wg = xcd_remap(blockIdx.x, nwg);
-    const int per_group = 16 * tiles_m, gid = wg / per_group, first_n = gid * 16;
-    const int gsz = min(16, tiles_n - first_n), within = wg - gid * per_group;
-    const int64_t m0 = (int64_t)(within / gsz) * 128, n0 = (int64_t)(first_n + within % gsz) * 128;
+    int tile_m, tile_n;
+    tile_of_block<16>(TileMap{tiles_m, tiles_n, nullptr}, tile_m, tile_n);
+    const int64_t m0 = (int64_t)tile_m * 128, n0 = (int64_t)tile_n * 128;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
@@ -299,12 +297,9 @@ __global__ __launch_bounds__(512) void cosine_gemm_f16_big_kernel(const _Float16
                                                                   const float* __restrict__ thr, uint8_t* __restrict__ gflag, int ngrp) {
     __shared__ __attribute__((aligned(16))) char S0[GSTAGE_B];
     __shared__ __attribute__((aligned(16))) char S1[GSTAGE_B];
-    const int nwg = tiles_m * tiles_n;
-    const int wg = xcd_remap(blockIdx.x, nwg);
-    constexpr int GN = 8;
-    const int per_group = GN * tiles_m, gid = wg / per_group, first_n = gid * GN;
-    const int gsz = min(GN, tiles_n - first_n), within = wg - gid * per_group;
-    const int64_t m0 = (int64_t)(within / gsz) * GBM, n0 = (int64_t)(first_n + within % gsz) * GBN;
+    int tile_m, tile_n;
+    tile_of_block<8>(TileMap{tiles_m, tiles_n, nullptr}, tile_m, tile_n);          // 8-wide n groups
+    const int64_t m0 = (int64_t)tile_m * GBM, n0 = (int64_t)tile_n * GBN;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3, l31 = lane & 31, half = lane >> 5;
@@ -450,6 +445,8 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(const _Float16* __rest
                                                           float* __restrict__ C, int64_t ldc, int tiles_m, int tiles_n,
                                                           const float* __restrict__ thr, uint8_t* __restrict__ gflag, int ngrp) {
     __shared__ __attribute__((aligned(1024))) char lds[2 * PP_BUF_B];       // the ONLY LDS object (a second one makes hipcc drain vmcnt before ds_reads)
+    // tile_of_block<8> spelled out: through the helper hipcc orders this kernel's scalar prologue differently, and the kernel is kept instruction for
+    // instruction (it is built without max-ILP and every change to it has to be measured on its own)
     const int nwg = tiles_m * tiles_n;
     const int wg = xcd_remap(blockIdx.x, nwg);
     constexpr int GN = 8;

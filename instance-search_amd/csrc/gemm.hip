@@ -118,39 +118,15 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
 
     const float* a_base = As + half * LDA + wm * (32 * TM) + l31;
     const float* b_base = Bs + half * LDB + wn * (32 * TN) + l31;
-    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4;
-    KtilePtrs<BK> pins;
-    if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
-
-    // outer loop: chunks of the two-level sum (one pass when CHUNK == 0); inner loop: the staged k-tiles of a chunk.  The FIRST k-tile of a chunk is
-    // a second copy of the body whose first MFMAs take C = 0 (no zeroing pass), the chain is added to tot behind the chunk's last barrier.
-    f32x16 (*totp)[TN] = nullptr;
-    if constexpr (CHUNK != 0) totp = tot;
-    auto body = [&](int kt, auto zero_c) {
-        const bool more = (kt + 1 < nk);
-        if (more) {
-            load_tile<ALIGNED, BM, BK>(Q, M, D, m0, (kt + 1) * BK, ra);
-            load_tile<ALIGNED, BN, BK>(G, N, D, n0, (kt + 1) * BK, rb);
-        }
-        mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
-        __syncthreads();
-        if (more) {
+    staged_kloop<TM, TN, BK, CHUNK>(a_base, b_base, nk, acc, tot,
+        [&](int kt) {
+            load_tile<ALIGNED, BM, BK>(Q, M, D, m0, kt * BK, ra);
+            load_tile<ALIGNED, BN, BK>(G, N, D, n0, kt * BK, rb);
+        },
+        [&]() {
             store_tile<BM, BK>(As, ra);
             store_tile<BN, BK>(Bs, rb);
-            __syncthreads();
-        }
-    };
-    if constexpr (CHUNK == 0) {
-        for (int kt = 0; kt < nk; ++kt) body(kt, std::false_type());
-    } else {
-        for (int kt = 0; kt < nk;) {
-            const int kend = kt + CHUNK / BK < nk ? kt + CHUNK / BK : nk;
-            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
-            for (; kt < kend; ++kt) body(kt, std::false_type());
-            if (!PINNED) add_chunk<TM, TN>(tot, acc);
-        }
-        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
-    }
+        });
     if (EPI == kEpiConv) ISX_STAMP(2);
     // the TN bias values of this lane's columns BEFORE everything else of the epilogue: a bias load behind the residual requests would make the first
     // add wait for all of them, and one between two tiles' stores would wait for those stores (vmcnt counts both on gfx9)
@@ -168,12 +144,6 @@ __device__ __forceinline__ void cosine_gemm_tile(float* __restrict__ lds, const 
             __builtin_amdgcn_sched_barrier(0);               // every load above the first store
             if (ISX_STAMPS) { ISX_STAMP_DRAIN(); ISX_STAMP(3); }
         }
-    }
-    if constexpr (CHUNK != 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];       // the epilogues below read acc
     }
 
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
@@ -293,17 +263,10 @@ template <bool ALIGNED>
 __global__ __launch_bounds__(256, kWgPerCu128) void conv1x1_tail_kernel(const float* __restrict__ Q, int64_t M, const float* __restrict__ G, int64_t N, int D,
                                                               float* __restrict__ C, int64_t ldc, TileMap tm_big, TileMap tm_small, int64_t m_split,
                                                               const float* __restrict__ bias, const float* __restrict__ residual, int relu) {
-    constexpr int kBig = 16 * (128 + 128 + 2 * lds_pad(16));
-    __shared__ float lds[kBig > kTailLdsFloats ? kBig : kTailLdsFloats];
-    const int nbig = tm_big.tiles_m * tm_big.tiles_n;                 // a multiple of 8: a block's XCD is the same in both numberings
-    int tile_m, tile_n;
-    if ((int)blockIdx.x < nbig) {
-        tile_of_block(tm_big, tile_m, tile_n, (int)blockIdx.x, nbig);
-        cosine_gemm_tile<ALIGNED, 2, 2, kEpiConv, 16>(lds, Q, M, G, N, D, C, ldc, (int64_t)tile_m * 128, (int64_t)tile_n * 128, bias, residual, relu);
-    } else {
-        tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
-        cosine_gemm_tile<ALIGNED, 1, 1, kEpiConv, 32>(lds, Q, M, G, N, D, C, ldc, m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64, bias, residual, relu);
-    }
+    __shared__ float lds[kTailKernelLdsFloats];
+    tail_tile_of_block(tm_big, tm_small, m_split, [&](auto T, auto BK, int64_t m0, int64_t n0) {
+        cosine_gemm_tile<ALIGNED, T(), T(), kEpiConv, BK()>(lds, Q, M, G, N, D, C, ldc, m0, n0, bias, residual, relu);
+    });
 }
 
 // rows covered by whole rounds of 128x128 tiles when the rest of the grid is a partial round (0: no split)
@@ -314,6 +277,16 @@ int64_t gemm_tail_split_rows(int64_t M, int64_t N, int64_t slots) {
     const int64_t rounds = tiles / slots, rem = tiles - rounds * slots;
     if (rounds < 1 || rem == 0 || rem > slots * 4 / 5) return 0;
     return rounds * (slots / tn) * 128;
+}
+TailGrid gemm_tail_grid(int64_t rows, int64_t N, int64_t split) {
+    TailGrid t;
+    t.big.m_active = t.small.m_active = nullptr;
+    t.big.tiles_m = (int)(split / 128);
+    t.big.tiles_n = (int)((N + 127) / 128);
+    t.small.tiles_m = (int)((rows - split + 63) / 64);          // (virtual rows: exact, isx_internal.hpp)
+    t.small.tiles_n = (int)((N + 63) / 64);
+    t.blocks = (unsigned)(t.big.tiles_m * t.big.tiles_n + t.small.tiles_m * t.small.tiles_n);
+    return t;
 }
 
 // ---- tile-shape selection ------------------------------------------------------------------
@@ -400,23 +373,17 @@ static int launch_gemm_any(const float* Q, int64_t M, const float* G, int64_t N,
     }
     if constexpr (EPI == kEpiConv) {
         if (best == 0 && split > 0) {
-            TileMap big, small;
-            big.m_active = small.m_active = nullptr;
-            big.tiles_m = (int)(split / 128); big.tiles_n = (int)((N + 127) / 128);
-            small.tiles_m = (int)((M - split + 63) / 64); small.tiles_n = (int)((N + 63) / 64);
-            const dim3 grid((unsigned)(big.tiles_m * big.tiles_n + small.tiles_m * small.tiles_n)), block(256);
-            if (aligned) hipLaunchKernelGGL((conv1x1_tail_kernel<true>), grid, block, 0, st, Q, M, G, N, D, C, ldc, big, small, split, ea.bias, ea.residual, ea.relu);
-            else hipLaunchKernelGGL((conv1x1_tail_kernel<false>), grid, block, 0, st, Q, M, G, N, D, C, ldc, big, small, split, ea.bias, ea.residual, ea.relu);
+            const TailGrid tg = gemm_tail_grid(M, N, split);
+            const dim3 grid(tg.blocks), block(256);
+            if (aligned) hipLaunchKernelGGL((conv1x1_tail_kernel<true>), grid, block, 0, st, Q, M, G, N, D, C, ldc, tg.big, tg.small, split, ea.bias, ea.residual, ea.relu);
+            else hipLaunchKernelGGL((conv1x1_tail_kernel<false>), grid, block, 0, st, Q, M, G, N, D, C, ldc, tg.big, tg.small, split, ea.bias, ea.residual, ea.relu);
             ISX_CHECK_LAUNCH("conv1x1_tail");
             return ISX_OK;
         }
     }
-    switch (best) {
-        case 0: launch_cfg<EPI, 2, 2, 16>(aligned16, Q, M, G, N, D, C, ldc, ea, st, m_active); break;
-        case 1: launch_cfg<EPI, 1, 2, 32>(aligned, Q, M, G, N, D, C, ldc, ea, st, m_active); break;
-        case 2: launch_cfg<EPI, 2, 1, 32>(aligned, Q, M, G, N, D, C, ldc, ea, st, m_active); break;
-        default: launch_cfg<EPI, 1, 1, 32>(aligned, Q, M, G, N, D, C, ldc, ea, st, m_active); break;
-    }
+    with_tile_shape(best, [&](auto TM, auto TN, auto BK) {          // (D % 16 == 0 is enough for the BK = 16 shape)
+        launch_cfg<EPI, TM(), TN(), BK()>(BK() == 16 ? aligned16 : aligned, Q, M, G, N, D, C, ldc, ea, st, m_active);
+    });
     ISX_CHECK_LAUNCH("cosine_gemm");
     return ISX_OK;
 }

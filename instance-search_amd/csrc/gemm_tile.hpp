@@ -1,5 +1,6 @@
 // gemm_tile.hpp -- device helpers shared by the fp32-MFMA GEMM (gemm.hip) and the implicit-GEMM 3x3 convolution
-// (conv.hip): XCD-aware tile mapping and the K-major LDS staging of operand tiles.
+// (conv.hip): XCD-aware tile mapping, the K-major LDS staging of operand tiles, the staged k loop with the two-level sum (staged_kloop) and the
+// block numbering of the 128x128 + 64x64 tail launches (tail_tile_of_block).
 #pragma once
 #include <type_traits>
 
@@ -11,26 +12,37 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int GROUP_N = 16;                     // n-tiles per scheduling group
 
-struct TileMap {
-    int tiles_m, tiles_n;
-    const int* m_active;       // optional device scalar: only rows < *m_active are live (fast.hip fallback)
-};
-
-// b / nwg: block index and block count of the tile range (defaults: the whole grid)
+// b / nwg: block index and block count of the tile range (defaults: the whole grid); GROUP: n-tiles per scheduling group
+template <int GROUP = GROUP_N>
 __device__ __forceinline__ void tile_of_block(const TileMap tm, int& tile_m, int& tile_n, int b, int nwg) {
     const int wg = xcd_remap(b, nwg);
-    // grouped order: GROUP_N n-tiles wide, all m-tiles tall, n fastest inside a group row
-    const int per_group = GROUP_N * tm.tiles_m;
+    // grouped order: GROUP n-tiles wide, all m-tiles tall, n fastest inside a group row
+    const int per_group = GROUP * tm.tiles_m;
     const int gid = wg / per_group;
-    const int first_n = gid * GROUP_N;
-    const int gsz = min(GROUP_N, tm.tiles_n - first_n);
+    const int first_n = gid * GROUP;
+    const int gsz = min(GROUP, tm.tiles_n - first_n);
     const int within = wg - gid * per_group;
     tile_m = within / gsz;
     tile_n = first_n + within % gsz;
 }
 
+template <int GROUP = GROUP_N>
 __device__ __forceinline__ void tile_of_block(const TileMap tm, int& tile_m, int& tile_n) {
-    tile_of_block(tm, tile_m, tile_n, (int)blockIdx.x, tm.tiles_m * tm.tiles_n);
+    tile_of_block<GROUP>(tm, tile_m, tile_n, (int)blockIdx.x, tm.tiles_m * tm.tiles_n);
+}
+
+// Tile-shape dispatch of the launchers: calls f(TM, TN, BK) -- std::integral_constants -- for shape `cfg` of pick_tile_cfg (0 = 128x128,
+// 1 = 64x128, 2 = 128x64, anything else = 64x64).  The ONE place that says which BK a shape runs with (BK = 16 for 128x128: gemm.hip's header).
+// MASK: the shapes the caller's kernel family is instantiated for (pick_tile_cfg's mask; the convolutions have no 64x128 instance).
+template <unsigned MASK = 0xF, class F>
+static inline void with_tile_shape(int cfg, F&& f) {
+    using std::integral_constant;
+    if (cfg == 0) return f(integral_constant<int, 2>(), integral_constant<int, 2>(), integral_constant<int, 16>());
+    if (cfg == 2) return f(integral_constant<int, 2>(), integral_constant<int, 1>(), integral_constant<int, 32>());
+    if constexpr ((MASK & 2u) != 0) {
+        if (cfg == 1) return f(integral_constant<int, 1>(), integral_constant<int, 2>(), integral_constant<int, 32>());
+    }
+    f(integral_constant<int, 1>(), integral_constant<int, 1>(), integral_constant<int, 32>());
 }
 
 // ROWS x BK k = ROWS*CH float4; thread t takes idx = j*256 + t: row = idx/CH, chunk = idx%CH.
@@ -236,6 +248,26 @@ constexpr int kWgPerCu128 = 2;      // resident workgroups per CU of the 128x128
 constexpr int kTailLdsFloats = 32 * (64 + 64 + 2);      // BK = 32 stage of a 64x64 tail tile of the 128x128 convolution launches (lds_pad(32) = 1 per operand)
 static_assert(kConvChunk % 32 == 0, "a chunk is a whole number of k-tiles");
 
+// ---- 128x128 tiles with a 64x64 tail in one grid (conv1x1_tail_kernel, conv3x3_tail_kernel, conv1x1_dual_tail_kernel; host side: gemm_tail_grid) ----
+// LDS of such a kernel: the larger of the BK = 16 stage of a 128x128 tile and the BK = 32 stage of a 64x64 tile
+constexpr int kBigLdsFloats = 16 * (128 + 128 + 2 * lds_pad(16));
+constexpr int kTailKernelLdsFloats = kBigLdsFloats > kTailLdsFloats ? kBigLdsFloats : kTailLdsFloats;
+// The tile of this block: the first tm_big.tiles_m * tm_big.tiles_n blocks are the 128x128 tiles of the rows below m_split, the rest are the 64x64
+// tiles of the rows from m_split on.  (The number of big tiles is a multiple of 8: a block's XCD is the same in both numberings.)
+// tile(T, BK, m0, n0) runs the (64 T) x (64 T) tile at row m0, column n0; T and BK are std::integral_constants (2, 16 or 1, 32).
+template <class Tile>
+__device__ __forceinline__ void tail_tile_of_block(const TileMap tm_big, const TileMap tm_small, int64_t m_split, Tile&& tile) {
+    const int nbig = tm_big.tiles_m * tm_big.tiles_n;
+    int tile_m, tile_n;
+    if ((int)blockIdx.x < nbig) {
+        tile_of_block(tm_big, tile_m, tile_n, (int)blockIdx.x, nbig);
+        tile(std::integral_constant<int, 2>(), std::integral_constant<int, 16>(), (int64_t)tile_m * 128, (int64_t)tile_n * 128);
+    } else {
+        tile_of_block(tm_small, tile_m, tile_n, (int)blockIdx.x - nbig, tm_small.tiles_m * tm_small.tiles_n);
+        tile(std::integral_constant<int, 1>(), std::integral_constant<int, 32>(), m_split + (int64_t)tile_m * 64, (int64_t)tile_n * 64);
+    }
+}
+
 // tot += acc (the chain of the chunk that just ended; acc itself is overwritten by the first MFMAs of the next chunk, which take C = 0)
 template <int TM, int TN>
 __device__ __forceinline__ void add_chunk(f32x16 (&tot)[TM][TN], const f32x16 (&acc)[TM][TN]) {
@@ -372,24 +404,72 @@ __device__ __forceinline__ void zero_tiles(f32x16 (&t)[TM][TN]) {
             for (int e = 0; e < 16; ++e) t[i][j][e] = 0.0f;
 }
 
-// Loop shape of the two-level sum (CHUNK terms per chain; 0 = one chain): the k loop is NESTED -- an outer loop over the chunks, the inner loop
-// over the CHUNK / BK k-tiles of a chunk is the plain staged loop of rounds 1-4 (loads of the next k-tile, MFMAs, barrier, LDS stores, barrier),
-// and fold_chunk runs between two inner loops:  tot = tot + acc;  acc = 0  (after the last chunk too: the value is tot).
-// Why nested (round 5 A/B on the 3x3 / dual families, ms per lab pass; one chain: 9.89 / 6.61): a conditional fold INSIDE the k loop cost 10-15 %
-// at any chunk length -- behind the MFMAs it needs 16 wait states and keeps hipcc from hoisting the loop's first barrier in between the last
-// MFMAs, the operand addresses were re-derived with a v_add_u32 per ds_read2 (11.13 / 7.56; addresses pinned: 10.85 / 7.29); in front of the
-// MFMAs hipcc duplicates the loop body and serialises the staging loads (11.37 / 7.61); C = 0 in the chunk's first MFMAs instead of zeroing
-// (two copies of the k-tile body) was slower still.
+// tot += acc;  acc = 0: the fold of the weight-gradient kernels (wgrad_kernel.hpp), whose k loops have a shape of their own
 template <int TM, int TN>
 __device__ __forceinline__ void fold_chunk(f32x16 (&tot)[TM][TN], f32x16 (&acc)[TM][TN]) {
     add_chunk<TM, TN>(tot, acc);
     zero_tiles(acc);
 }
-// PINNED (the 128x128 shape): the k-tile adds the previous chunk's chain to tot itself; otherwise the caller folds with add_chunk behind the chunk
+// PINNED (the 128x128 shape): the k-tile adds the previous chunk's chain to tot itself; otherwise staged_kloop folds with add_chunk behind the chunk
 template <int TM, int TN, int BK, int LDA, int LDB, bool PINNED, bool ZERO_C = false>
 __device__ __forceinline__ void mfma_ktile_sel(const float* __restrict__ a_base, const float* __restrict__ b_base, const KtilePtrs<BK>& pins, f32x16 (&acc)[TM][TN],
                                                f32x16 (*tot)[TN] = nullptr) {
     if constexpr (PINNED) mfma_ktile_pinned<TM, TN, BK, ZERO_C>(pins, acc, tot);
     else mfma_ktile<TM, TN, BK, LDA, LDB, ZERO_C>(a_base, b_base, acc);
+}
+
+// ---- THE staged k loop of the fp32 tile kernels (cosine_gemm_tile, conv1x1_dual_tile, the plain path of conv3x3_mainloop) -----------------------
+// Per k-tile kt: request k-tile kt + 1 into the caller's staging registers (load_next(kt + 1)), run the MFMAs of k-tile kt out of the LDS,
+// barrier, write the staged registers to the LDS (store_staged()), barrier.  The caller has k-tile 0 in the LDS (the K-major images of a
+// (64 TM) x BK and a (64 TN) x BK operand tile, store_tile) behind a barrier, and acc zeroed; every wave has left the LDS on return.
+// a_base / b_base: this lane's first operand element in the two images (mfma_ktile).  They come from the caller, next to the lane arithmetic of
+// its epilogue: derived here a second time, hipcc shared less of that arithmetic and several instances moved by registers and scratch (round 8).
+// CHUNK != 0: the two-level sum -- terms per first-level chain; tot (zeroed by the caller) collects the chains and acc returns their sum.
+// CHUNK == 0: one chain over all nk k-tiles in acc (scores, gradients); tot is a dummy.
+// The shape of the chunked loop is what round 5 paid for (A/B on the 3x3 / dual families, ms per lab pass; one chain: 9.89 / 6.61):
+//  * NESTED: an outer loop over the chunks, the inner loop over the CHUNK / BK k-tiles of a chunk is the plain staged loop of rounds 1-4.  A
+//    conditional fold INSIDE one k loop cost 10-15 % at any chunk length: behind the MFMAs it needs 16 wait states and keeps hipcc from hoisting
+//    the loop's first barrier in between the last MFMAs (11.13 / 7.56; with the addresses pinned 10.85 / 7.29); in front of the MFMAs hipcc
+//    duplicates the loop body and serialises the staging loads (11.37 / 7.61).
+//  * C = 0: the FIRST k-tile of a chunk is a second copy of the body whose first MFMAs take C = 0 as an inline constant -- no zeroing pass
+//    (fold between the inner loops 10.63 / 7.15, with the C = 0 start 10.41 / 6.97).
+//  * PINNED operand addresses for the 128x128 shape (pin_ktile_ptrs: without them hipcc re-derived every address with a v_add_u32 per ds_read2),
+//    whose C = 0 k-tile also adds the PREVIOUS chunk's chain to tot in place, tile by tile in front of the MFMA that restarts the tile
+//    (add_tile_inplace: 3x3 10.49 -> 10.22, dual 7.04 -> 6.96; it loses on the smaller tiles, which fold with add_chunk behind the chunk).
+//  * the LAST chunk's add_chunk of the pinned shape stands outside the loop: there is no next C = 0 k-tile to carry it.
+template <int TM, int TN, int BK, int CHUNK, class LoadNext, class StoreStaged>
+__device__ __forceinline__ void staged_kloop(const float* a_base, const float* b_base, int nk, f32x16 (&acc)[TM][TN],
+                                             f32x16 (&tot)[CHUNK ? TM : 1][CHUNK ? TN : 1], LoadNext&& load_next, StoreStaged&& store_staged) {
+    constexpr int LDA = 64 * TM + lds_pad(BK), LDB = 64 * TN + lds_pad(BK);
+    constexpr bool PINNED = CHUNK != 0 && TM * TN == 4;
+    KtilePtrs<BK> pins;
+    if constexpr (PINNED) pins = pin_ktile_ptrs<BK, LDA, LDB>(a_base, b_base);
+    f32x16 (*totp)[TN] = nullptr;
+    if constexpr (CHUNK != 0) totp = tot;
+    auto body = [&](int kt, auto zero_c) {
+        const bool more = (kt + 1 < nk);
+        if (more) load_next(kt + 1);
+        mfma_ktile_sel<TM, TN, BK, LDA, LDB, PINNED, decltype(zero_c)::value>(a_base, b_base, pins, acc, totp);
+        __syncthreads();
+        if (more) {
+            store_staged();
+            __syncthreads();
+        }
+    };
+    if constexpr (CHUNK == 0) {
+        for (int kt = 0; kt < nk; ++kt) body(kt, std::false_type());
+    } else {
+        for (int kt = 0; kt < nk;) {
+            const int kend = kt + CHUNK / BK < nk ? kt + CHUNK / BK : nk;
+            body(kt++, std::true_type());                      // (PINNED: adds the PREVIOUS chunk's chain in front of its C = 0 MFMAs)
+            for (; kt < kend; ++kt) body(kt, std::false_type());
+            if (!PINNED) add_chunk<TM, TN>(tot, acc);
+        }
+        if (PINNED) add_chunk<TM, TN>(tot, acc);       // the last chunk
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];       // the tile's value: the sum of the chunk sums (the epilogues read acc)
+    }
 }
 }  // namespace isx

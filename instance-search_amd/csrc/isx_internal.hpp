@@ -43,6 +43,17 @@ int launch_gemm_masked(const float* A, int64_t M, const float* Bt, int64_t N, in
 // partial round -- the caller runs the remaining rows as 64x64 tiles in the same grid; 0 = no split.  g_tail_split: debug / A-B switch.
 extern std::atomic<int> g_tail_split;      // (the debug / A-B knobs are relaxed atomics: a test thread may flip them while another thread launches)
 int64_t gemm_tail_split_rows(int64_t M, int64_t N, int64_t slots = 1024);       // slots: resident 128x128 workgroups of the calling kernel (256 CUs x workgroups per CU)
+// Tile grid of a kernel: tiles_m x tiles_n tiles, numbered by tile_of_block (gemm_tile.hpp)
+struct TileMap {
+    int tiles_m, tiles_n;
+    const int* m_active;       // optional device scalar: only rows < *m_active are live (fast.hip fallback)
+};
+// Grid of a launch with such a tail: `big` = the 128x128 tiles of the rows below `split` (> 0, from gemm_tail_split_rows: a multiple of 128),
+// `small` = the 64x64 tiles of the rows from `split` on, blocks = the tiles of both.  rows: the REAL row count M, whose last tail tile may be
+// partial -- the count rounds up -- or the VIRTUAL row count of a position-major 3x3 launch (conv3x3_tile.hpp), a multiple of 128: there the
+// 64-row tail tiles divide the rest exactly, and the same rounding is exact.
+struct TailGrid { TileMap big, small; unsigned blocks; };
+TailGrid gemm_tail_grid(int64_t rows, int64_t N, int64_t split);
 // Tile shape (0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64) with the smallest estimated launch time among those in `mask` (rounds of resident
 // workgroups + tail + per-CU quantisation, gemm.hip); eff[4]: steady-state efficiency per shape of the calling kernel family.
 int pick_tile_cfg(int64_t M, int64_t N, int64_t split, const float* eff, unsigned mask, int wg_per_cu_128 = 4);
