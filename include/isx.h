@@ -53,23 +53,36 @@ int isx_version(void);
 /* ---- descriptor head ------------------------------------------------------- */
 
 /* model/custom_modules.py:52-57 NormalizeL2Fun.forward: y = x / sqrt(sum_j x_j^2 + eps),
- * eps INSIDE the sqrt.  x, y: (B, D).  In-place (y == x) allowed. */
+ * eps INSIDE the sqrt.  x, y: (B, D).  In-place (y == x) allowed.
+ * The sum of squares is one of three fixed orders, chosen by (D, 16-byte alignment of x, y and shift) and by nothing else -- not B, not the
+ * neighbouring rows: D % 4 == 0, aligned, D <= 2048: one wave per row, lane l adds the float4 terms x^2 + y^2 + z^2 + w^2 of float4 l, l + 64,
+ * ..., xor butterfly 32 .. 1; D % 4 == 0, aligned, larger: 1024 threads, thread t the float4 terms t, t + 1024, ..., the butterfly per wave, the
+ * 16 wave sums in order; otherwise the same with single elements -- and there a quotient of -0 comes out as +0 when there is no Shift.  The
+ * same row at another alignment may therefore differ in the last bit. */
 int isx_l2norm_rows(const float* x, int64_t B, int64_t D, float eps, float* y, isx_stream_t stream);
 
 /* model/siamese.py:110-113 feature_reduc1[0:2] = NormalizeL2 -> Shift
  * (custom_modules.py:52-57 then :16-18): y = x / sqrt(sum x^2 + eps) + shift.
- * shift: (F) or NULL.  x, y: (B, F). */
+ * shift: (F) or NULL.  x, y: (B, F).  Same kernels and orders as isx_l2norm_rows; the Shift is added to the rounded quotient. */
 int isx_l2norm_shift_rows(const float* x, const float* shift, int64_t B, int64_t F, float eps, float* y,
                           isx_stream_t stream);
 
 /* model/siamese.py:49-54 TuneClassif.forward with the classifier stripped
  * (train/classif_finetune.py:87-90) + NormalizeL2Fun (:100): global average pool over
- * the whole HxW map, flatten, L2.  fmap: (B,C,H,W) NCHW; y: (B,C). */
+ * the whole HxW map, flatten, L2.  fmap: (B,C,H,W) NCHW; y: (B,C).
+ * A channel's mean is the in-order sum of its H*W values / (float)(H*W); thread t of 256 adds the squared means of channels t, t + 256, ...,
+ * butterfly per wave, the 4 wave sums in order.  Maps whose channels do not fit the staging (decided by (C, H*W) alone) pool each channel
+ * lane-strided + butterfly instead and normalise with the isx_l2norm_rows kernel that (C, alignment of y) selects.  An image's descriptor
+ * depends on the image and (C, H*W) -- never on B or on the other images of the launch. */
 int isx_gap_l2(const float* fmap, int64_t B, int C, int H, int W, float eps, float* y, isx_stream_t stream);
 
 /* Same operation on a channels-last feature map: fmap is (B,H,W,C) in memory (torch
  * memory_format=channels_last of a logical (B,C,H,W) tensor), which is what the NHWC convolution
- * kernels of the backbone produce.  Same summation order, same result.  y: (B,C). */
+ * kernels of the backbone produce.  y: (B,C).  The pooled means are those of isx_gap_l2 bit for bit (in-order sums); the sum of squares is
+ * NOT in its order -- thread t of 512 adds the float4 terms of channels 4t .. 4t + 3, 4(t + 512) .., butterfly per wave, the 8 wave sums in
+ * order -- so the two entries agree to a few ulp (tests: rtol 2e-6), not to the bit.  C % 4 != 0, C > 8192 or a map / y off a 16-byte boundary:
+ * one thread per channel pools in order, then the isx_l2norm_rows kernel that (C, alignment of y) selects.  Bits depend on the image, C and
+ * those alignments, never on B. */
 int isx_gap_l2_nhwc(const float* fmap, int64_t B, int C, int H, int W, float eps, float* y, isx_stream_t stream);
 
 /* Fused epilogue of the inference trunk's convolutions (BatchNorm folded, model/nn_utils.py fold_batch_norm):
@@ -157,7 +170,8 @@ int isx_boxpool_s1_nhwc(const float* fmap, int64_t B, int C, int H, int W, int k
 
 /* train/classif_regions.py:118-128: class-max map, spatial arg-max (smallest column,
  * then smallest row on ties), gather the K class scores there, L2.
- * cls: (B,K,Hp,Wp); desc: (B,K); loc: (B,2) = {row i1, col i2}. */
+ * cls: (B,K,Hp,Wp); desc: (B,K); loc: (B,2) = {row i1, col i2}.  -0 and +0 are one score.  Sum of squares: thread t of 256 adds classes
+ * t, t + 256, ..., butterfly per wave, the 4 wave sums in order; a function of the image's K scores there (the NHWC entry gives the same bits). */
 int isx_best_location_desc(const float* cls, int64_t B, int K, int Hp, int Wp, float eps, float* desc,
                            int64_t* loc, isx_stream_t stream);
 
@@ -170,7 +184,9 @@ int isx_region_topk(const float* cls, int64_t B, int K, int Hp, int Wp, int k, i
 /* model/siamese.py:199-219: for each of the k windows of each image, (row,col) = (idx / Wp, idx % Wp):
  * x[b, :, row:row+kh, col:col+kw] flattened (C,h,w) -> NormalizeL2 -> Shift.
  * fmap: (B,C,Hf,Wf); flat_idx: (B,k); rows: (B, k, C*kh*kw); shift (C*kh*kw) or NULL.
- * Windows with flat_idx < 0 produce zero rows.  The caller applies the Linear ONCE to all B*k rows
+ * Windows with flat_idx < 0 or past the map produce zero rows (+0).  Sum of squares: thread t of 1024 adds elements t, t + 1024, ... of the
+ * (C,h,w) row, butterfly per wave, the 16 wave sums in order; the NHWC entry walks its (h,w,C) row in float4s t, t + 1024, ... and adds the
+ * four squares one by one -- another order, and another element order of the row.  A row's bits depend on its window alone.  The caller applies the Linear ONCE to all B*k rows
  * (the 100352 x D weight is then streamed once per batch, not once per window as in the reference). */
 int isx_region_gather_l2(const float* fmap, int64_t B, int C, int Hf, int Wf, int kh, int kw, const int64_t* flat_idx, int k,
                          int Wp, const float* shift, float eps, float* rows, isx_stream_t stream);
@@ -178,7 +194,8 @@ int isx_region_gather_l2(const float* fmap, int64_t B, int C, int Hf, int Wf, in
 /* Channels-last variants of the three region entry points above (same reference lines, same selection and tie-break):
  * cls: (B,Hp,Wp,K) -- the output of the 1x1-convolution classifier on the NHWC trunk --, fmap: (B,Hf,Wf,C).
  * isx_region_gather_l2_nhwc keeps a window in (h,w,C) order: rows (B,k,kh*kw*C), row[(a*kw + b)*C + c] = x[b, c, row+a, col+b];
- * shift_hwc is the Shift parameter permuted the same way (the caller permutes the Linear's weight columns once to match). */
+ * shift_hwc is the Shift parameter permuted the same way (the caller permutes the Linear's weight columns once to match).
+ * isx_best_location_desc_nhwc gives the bits of the NCHW entry; the rows of isx_region_gather_l2_nhwc agree with the NCHW entry's to a few ulp. */
 int isx_best_location_desc_nhwc(const float* cls, int64_t B, int K, int Hp, int Wp, float eps, float* desc,
                                 int64_t* loc, isx_stream_t stream);
 int isx_region_topk_nhwc(const float* cls, int64_t B, int K, int Hp, int Wp, int k, int64_t* flat_idx, float* score,
@@ -402,7 +419,9 @@ int isx_boxpool_s1_bwd_nhwc(const float* g, int64_t B, int C, int H, int W, int 
 int isx_linear_wgrad_leaves(const float* dy, const float* x, int leaves, int R, int N, int K, float* dw, isx_stream_t stream);
 
 /* model/custom_modules.py:59-67 NormalizeL2Fun.backward: with n2 = sum_j x_j^2 + eps and c = sum_j x_j dy_j,
- * dx = (n2 dy - x c) / (n2 sqrt(n2)).  x, dy, dx: (B, D). */
+ * dx = (n2 dy - x c) / (n2 sqrt(n2)), computed as (n2 dy - x c) * inv with inv = 1 / (n2 sqrt(n2)).  x, dy, dx: (B, D).  Both sums:
+ * thread t of 1024 adds the products of elements t, t + 1024, ..., butterfly per wave, the 16 wave sums in order -- one order for every D and
+ * alignment; a row's bits depend on that row alone. */
 int isx_l2norm_rows_bwd(const float* x, const float* dy, int64_t B, int64_t D, float eps, float* dx, isx_stream_t stream);
 
 /* ---- backward pass of the TRAINABLE trunk suffix (siamese training, reference configuration) ---------------------------------

@@ -86,8 +86,12 @@ __global__ __launch_bounds__(1024) void l2norm_rows_block_kernel(const float* __
 // the CP*HW floats of a pass are contiguous in NCHW, so they are streamed into LDS
 // with 16-B coalesced loads; thread c then sums its channel's HW values IN ORDER (the
 // summation order of torch's CPU avg_pool2d, so pooled values are bit-identical to
-// the oracle's).  LDS channel stride is HW|1 (odd) -> conflict-free ds_read_b32.
-// Pooled values stay in registers (<= MAXP passes); sum of squares by butterfly.
+// the oracle's; the gap_only_kernel fallback below pools in another order).  LDS
+// channel stride is HW|1 (odd) -> conflict-free ds_read_b32.  Pooled values stay in
+// registers (<= MAXP passes) until the last pass is consumed, then go to the front of
+// the LDS: thread t squares channels t, t+256, ... WHATEVER CP WAS, so that the sum of
+// squares (block_sum<256>) and with it every descriptor bit is a function of the image
+// and (C, HW) alone -- the launcher picks CP by the size of the launch.
 constexpr int kGapThreads = 256;
 constexpr int kGapMaxPasses = 16;
 
@@ -100,7 +104,6 @@ __global__ __launch_bounds__(kGapThreads) void gap_l2_kernel(const float* __rest
     const float* img = fmap + (int64_t)blockIdx.x * C * HW;
     const float inv_div = (float)HW;
     float pooled[kGapMaxPasses];
-    float ss = 0.0f;
     const int passes = (C + CP - 1) / CP;
 #pragma unroll 1
     for (int p = 0; p < passes; ++p) {
@@ -144,16 +147,20 @@ __global__ __launch_bounds__(kGapThreads) void gap_l2_kernel(const float* __rest
         // static register index (guide rule 20): unrolled select
 #pragma unroll
         for (int q = 0; q < kGapMaxPasses; ++q) if (q == p) pooled[q] = s;
-        ss += s * s;
     }
-    ss = block_sum<kGapThreads>(ss, red);
-    const float n = sqrtf(ss + eps);
-    float* yr = y + (int64_t)blockIdx.x * C;
+    __syncthreads();   // last pass fully consumed: the staging area now takes the C pooled values (the host sized it for them)
 #pragma unroll
     for (int q = 0; q < kGapMaxPasses; ++q) {
         const int c = q * CP + tid;
-        if (q < passes && tid < CP && c < C) yr[c] = pooled[q] / n;
+        if (q < passes && tid < CP && c < C) lds[c] = pooled[q];
     }
+    __syncthreads();
+    float ss = 0.0f;
+    for (int c = tid; c < C; c += kGapThreads) ss += lds[c] * lds[c];
+    ss = block_sum<kGapThreads>(ss, red);
+    const float n = sqrtf(ss + eps);
+    float* yr = y + (int64_t)blockIdx.x * C;
+    for (int c = tid; c < C; c += kGapThreads) yr[c] = lds[c] / n;
 }
 
 // ------------------------------------------------------------------ gap_l2 (NHWC) --
@@ -224,8 +231,8 @@ __global__ __launch_bounds__(256) void gap_only_nhwc_kernel(const float* __restr
     }
 }
 
-// Fallback for huge maps / channel counts: wave per (image, channel) sum, pooled written
-// to y, then the row kernel normalises in place.
+// Fallback for huge maps / channel counts: wave per (image, channel) sum -- lane-strided, then the butterfly: NOT the in-order sum of
+// the fused kernel --, pooled written to y, then the row kernel normalises in place.  Taken by (C, HW) alone.
 __global__ __launch_bounds__(256) void gap_only_kernel(const float* __restrict__ fmap, int64_t BC, int HW,
                                                        float* __restrict__ y) {
     const int lane = threadIdx.x & 63;
@@ -382,12 +389,19 @@ ISX_API int isx_gap_l2(const float* fmap, int64_t B, int C, int H, int W, float 
     hipStream_t st = (hipStream_t)stream;
     const int HW = H * W;
     const int stride = HW | 1;
-    // 26 KB per workgroup (6 per CU) keeps more loads in flight: 4.6-5.4 TB/s vs 3.3-4.2 with 52 KB at
-    // B >= 1024; small batches have too few workgroups for that to matter and prefer fewer passes
-    const size_t budget = (B >= 512 ? 26 : 52) * 1024;
-    int CP = kGapThreads;
-    while (CP > 32 && (size_t)CP * stride * 4 > budget) CP >>= 1;
-    const bool fits = (size_t)CP * stride * 4 <= budget && (C + CP - 1) / CP <= kGapMaxPasses;
+    // The PATH is chosen from (C, HW) alone, on the 52 KB budget: an image's descriptor must not depend on the launch it is part of.
+    // 26 KB per workgroup (6 per CU) keeps more loads in flight: 4.6-5.4 TB/s vs 3.3-4.2 with 52 KB at B >= 1024; small batches have too
+    // few workgroups for that to matter and prefer fewer passes.  So launches of 512 images or more take the 26 KB CP where that fits too;
+    // CP only sets how the map is staged, the kernel's sums do not depend on it.
+    const auto cp_for = [&](size_t budget) {
+        int cp = kGapThreads;
+        while (cp > 32 && (size_t)cp * stride * 4 > budget) cp >>= 1;
+        return cp;
+    };
+    const auto fits_in = [&](int cp, size_t budget) { return (size_t)cp * stride * 4 <= budget && (C + cp - 1) / cp <= kGapMaxPasses; };
+    int CP = cp_for(52 * 1024);
+    const bool fits = fits_in(CP, 52 * 1024);
+    if (fits && B >= 512 && fits_in(cp_for(26 * 1024), 26 * 1024)) CP = cp_for(26 * 1024);
     if (!fits) {
         const int64_t BC = B * C;
         hipLaunchKernelGGL(gap_only_kernel, dim3((unsigned)((BC + 3) / 4)), dim3(256), 0, st, fmap, BC, HW, y);
@@ -395,7 +409,7 @@ ISX_API int isx_gap_l2(const float* fmap, int64_t B, int C, int H, int W, float 
         return launch_l2norm(y, nullptr, B, C, eps, y, st);
     }
     const bool vec = ((uintptr_t)fmap % 16 == 0) && (((int64_t)C * HW) % 4 == 0) && (((int64_t)CP * HW) % 4 == 0);
-    const size_t lds = (size_t)CP * stride * 4;
+    const size_t stage = (size_t)CP * stride * 4, lds = stage > (size_t)C * 4 ? stage : (size_t)C * 4;   // C <= 16 CP floats: at most 16 KB
     if (vec) hipLaunchKernelGGL(gap_l2_kernel<true>, dim3((unsigned)B), dim3(kGapThreads), lds, st, fmap, C, HW, CP, stride, eps, y);
     else hipLaunchKernelGGL(gap_l2_kernel<false>, dim3((unsigned)B), dim3(kGapThreads), lds, st, fmap, C, HW, CP, stride, eps, y);
     ISX_CHECK_LAUNCH("isx_gap_l2");
