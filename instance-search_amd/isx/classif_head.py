@@ -29,12 +29,6 @@ order); the 3.8 MB weight gets an ordinary per-leaf gradient there: nothing is d
 import torch
 
 from . import _lib, ops
-from ._lib import check, lib
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
 
 MAX_ROWS_PER_LEAF = 8192          # isx_softmax_xent_leaves keeps a leaf's row losses in LDS
 
@@ -43,6 +37,9 @@ class ClassifHeadEngine(object):
     def __init__(self, net):
         self.pool = net.feature_reduc[0]
         self.cls = net.classifier[0]                   # nn.Linear (N, K) or 1x1 PointwiseConv (N, K, 1, 1): the same (N, K) matrix
+
+    def built_for(self, net):
+        return self.cls is net.classifier[0] and self.pool is net.feature_reduc[0]
 
     @staticmethod
     def applicable(net):
@@ -118,18 +115,11 @@ class ClassifHeadEngine(object):
             lo, hi = slices[cls.weight]
             flat_all[:, lo:hi] += ops.linear_wgrad_leaves(dz, rows, leaves).view(leaves, -1)
         if cls.bias is not None and cls.bias.requires_grad:
-            gb = torch.empty((leaves, N), dtype=torch.float32, device=dz.device)
-            check(lib().isx_colsum_leaves(dz.data_ptr(), leaves, R, N, gb.data_ptr(), _stream()), "isx_colsum_leaves")
             lo, hi = slices[cls.bias]
-            flat_all[:, lo:hi] += gb
+            flat_all[:, lo:hi] += ops.colsum_leaves(dz, leaves)
         if not need_dy:
             return per_leaf, None
-        Mr = M * loc
-        Mp = (Mr + 63) // 64 * 64
-        dzT = dz.new_zeros((Np, Mp))                            # padding classes and rows: zero products leave every chain untouched
-        dzT[:N, :Mr] = dz.t()
-        dpool = torch.empty((Mp, K), dtype=torch.float32, device=dz.device)
-        check(lib().isx_head_linear_dgrad(dzT.data_ptr(), Mp, Np, wp.data_ptr(), K, dpool.data_ptr(), _stream()), "isx_head_linear_dgrad")
+        dpool = ops.head_linear_dgrad(dz, wp)                   # (M loc, K); against the class-padded weight
         if loc == 1:                                            # the window spans the map: one term per pixel, the division alone
-            return per_leaf, ops.gap_bwd_nhwc(dpool[:M], H, W)
-        return per_leaf, ops.boxpool_s1_bwd_nhwc(dpool[:Mr].view(M, Ho, Wo, K).permute(0, 3, 1, 2), H, W, kh, kw)
+            return per_leaf, ops.gap_bwd_nhwc(dpool, H, W)
+        return per_leaf, ops.boxpool_s1_bwd_nhwc(dpool.view(M, Ho, Wo, K).permute(0, 3, 1, 2), H, W, kh, kw)

@@ -19,11 +19,6 @@ gradients of a micro-batch are the same bits whether 1 or 8 micro-batches share 
 import torch
 
 from . import _lib, ops
-from ._lib import check, lib
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class HeadEngine(object):
@@ -32,6 +27,9 @@ class HeadEngine(object):
         self.shift = net.feature_reduc1[1]
         self.lin = net.feature_reduc1[2]
         self._ws = None
+
+    def built_for(self, net):
+        return self.lin is net.feature_reduc1[2] and self.shift is net.feature_reduc1[1]
 
     @staticmethod
     def applicable(net):
@@ -70,11 +68,9 @@ class HeadEngine(object):
         go to row l of flat_all (per-leaf flat gradient buffers) at the parameters' slices, the Linear's (x, dy) rows to `sink`.
         Returns the gradient wrt the trunk output, shaped (M, C, h, w)."""
         x0, x1, y, shape, shard, sctx = ctx
-        M, K = x1.shape
+        M = x1.size(0)
         lin = self.lin
-        N = lin.out_features
-        R = M // leaves
-        if R * leaves != M:
+        if M % leaves:
             raise _lib.IsxError("head engine: %d rows are not %d equal micro-batches" % (M, leaves))
         dy = ops.l2norm_rows_bwd(y, dd.contiguous())
         if lin.weight.requires_grad and shard is None:
@@ -82,26 +78,14 @@ class HeadEngine(object):
                 raise _lib.IsxError("head engine: the Linear weight needs the training step's RowSink")
             sink.add(lin.weight, x1, dy)
         if lin.bias is not None and lin.bias.requires_grad:
-            gb = torch.empty((leaves, N), dtype=torch.float32, device=dy.device)
-            check(lib().isx_colsum_leaves(dy.data_ptr(), leaves, R, N, gb.data_ptr(), _stream()), "isx_colsum_leaves")
             lo, hi = slices[lin.bias]
-            flat_all[:, lo:hi].copy_(gb)
+            flat_all[:, lo:hi].copy_(ops.colsum_leaves(dy, leaves))
         if shard is not None:
             dx1 = shard.backward(sctx, dy).contiguous()        # every rank's chains of its feature groups, this rank's rows summed in group order
         else:
-            Mp = (M + 63) // 64 * 64
-            if Mp == M:
-                dyT = dy.t().contiguous()
-            else:
-                dyT = dy.new_zeros((N, Mp))
-                dyT[:, :M] = dy.t()
-            dx1 = torch.empty((Mp, K), dtype=torch.float32, device=dy.device)
-            check(lib().isx_head_linear_dgrad(dyT.data_ptr(), Mp, N, lin.weight.data_ptr(), K, dx1.data_ptr(), _stream()), "isx_head_linear_dgrad")
-            dx1 = dx1[:M]
+            dx1 = ops.head_linear_dgrad(dy, lin.weight.detach())
         if self.shift.param.requires_grad:
-            gs = torch.empty((leaves, K), dtype=torch.float32, device=dy.device)
-            check(lib().isx_colsum_leaves(dx1.data_ptr(), leaves, R, K, gs.data_ptr(), _stream()), "isx_colsum_leaves")
             lo, hi = slices[self.shift.param]
-            flat_all[:, lo:hi].copy_(gs)
+            flat_all[:, lo:hi].copy_(ops.colsum_leaves(dx1, leaves))
         dx0 = ops.l2norm_rows_bwd(x0, dx1)
         return dx0.view(shape)

@@ -1,7 +1,7 @@
 """Thin torch-tensor wrappers over the C ABI (include/isx.h).  One function per entry.
 
-All tensors must live on the GPU; work is enqueued on torch's current stream.  These are
-the only places the product path touches ctypes."""
+All tensors must live on the GPU; work is enqueued on torch's current stream.  The product
+path touches ctypes here and, for the entries they alone use, in isx/suffix.py, isx/shard_head.py and isx/dp.py."""
 import torch
 
 from . import _lib
@@ -917,6 +917,38 @@ def linear_wgrad_leaves(dy, x, leaves):
     dw = torch.empty((leaves, N, K), device=dy.device, dtype=torch.float32)
     check(lib().isx_linear_wgrad_leaves(dy.data_ptr(), x.data_ptr(), leaves, M // leaves, N, K, dw.data_ptr(), _stream()), "isx_linear_wgrad_leaves")
     return dw
+
+
+def colsum_leaves(x, leaves):
+    """Column sums of `leaves` consecutive groups of rows, each over its rows in order (isx_colsum_leaves): x (leaves * R, C) -> (leaves, C)."""
+    x = _f32(x, "x")
+    M, Cc = x.shape
+    if leaves <= 0 or M % leaves:
+        raise _lib.IsxError("colsum_leaves: %d rows do not split into %d equal leaves" % (M, leaves))
+    out = torch.empty((leaves, Cc), device=x.device, dtype=torch.float32)
+    check(lib().isx_colsum_leaves(x.data_ptr(), leaves, M // leaves, Cc, out.data_ptr(), _stream()), "isx_colsum_leaves")
+    return out
+
+
+def head_linear_dgrad(dy, weight):
+    """dx = dy W (isx_head_linear_dgrad: the TN kernel on (dy^T, W)).  dy: (M, N); weight: (Np, K) with Np >= N -- a copy the caller has
+    zero-padded where N is off the kernel's granule.  The kernel reads dy transposed with the rows padded to a multiple of 64: the (Np, Mp)
+    operand is built here, padding classes and rows zero (zero products leave every chain untouched); without either padding it is
+    `dy.t().contiguous()`, no zero-fill.  Returns the first M rows, (M, K)."""
+    dy, weight = _f32(dy, "dy"), _f32(weight, "weight")
+    M, N = dy.shape
+    Np, K = weight.shape
+    if Np < N:
+        raise _lib.IsxError("head_linear_dgrad: dy %s has more columns than weight %s has rows" % (tuple(dy.shape), tuple(weight.shape)))
+    Mp = (M + 63) // 64 * 64
+    if Mp == M and Np == N:
+        dyT = dy.t().contiguous()
+    else:
+        dyT = dy.new_zeros((Np, Mp))
+        dyT[:N, :M] = dy.t()
+    dx = torch.empty((Mp, K), device=dy.device, dtype=torch.float32)
+    check(lib().isx_head_linear_dgrad(dyT.data_ptr(), Mp, Np, weight.data_ptr(), K, dx.data_ptr(), _stream()), "isx_head_linear_dgrad")
+    return dx[:M]
 
 
 # ---- half-precision filter path (csrc/fast.hip) ----------------------------------------------------

@@ -83,7 +83,84 @@ def _convolutionalize_classifier(classifier, feature_size2d, has_reduc):
             seen += 1
 
 
-class TuneClassif(nn.Module):
+class TrunkHooks(nn.Module):
+    """What a net offers the training step (utils/train_general._Stepper) beyond forward(): its _SplitTrunk (`_trunk`: a plain attribute, so
+    it stays out of state_dict() and is copied by copy.deepcopy) and the hooks that need nothing but it and `features` -- trunk_precomputable,
+    precompute_trunk, suffix_engine and the gate of the tail engines.  What differs per net stays with the net: forward, forward_features,
+    head_rows, and which tail engine it has (head_engine / classif_head_engine: None here)."""
+    branches_are_scales = False     # (TuneClassifSub: True)
+
+    def __init__(self):
+        super().__init__()
+        self._trunk = _SplitTrunk()
+
+    def trunk_precomputable(self):
+        """True when precompute_trunk can serve training steps: training mode, GPU, a frozen trunk prefix, BatchNorm not learning."""
+        p = next(self.features.parameters(), None)
+        return bool(self.training and p is not None and p.is_cuda and _SplitTrunk.enabled(self.features))
+
+    def precompute_trunk(self, *xs, cache=False):
+        """Training with a frozen trunk PREFIX and frozen BatchNorm (the reference's configurations: stem + layers 1-3 frozen, layer4
+        trained; or everything frozen with untrained = -1): the prefix output of an image does not depend on the batch it rides in and needs
+        no autograd graph, so the prefix of a whole mini-batch runs as ONE launch of the folded inference trunk instead of once per
+        micro-batch of 8 triplets (24 images: far too few to fill the chip).  Returns the prefix feature tensors of the given image batches
+        (same split), or None when the trunk has to run inside the step (nothing frozen, BatchNorm learning, CPU tensors, eval mode).
+        branches_are_scales: the batches are the scales of the same images and differ in spatial size -- equal batch sizes instead of equal
+        shapes, one launch PER SCALE, and no `cache` (the prefix-feature table of a resident set holds one size only)."""
+        if not self.training or not xs or not all(x.is_cuda and x.dtype == torch.float32 for x in xs):
+            return None
+        same = (lambda x: x.size(0)) if self.branches_are_scales else (lambda x: tuple(x.shape[1:]))
+        if not self._trunk.usable(self.features, xs[0]) or len(set(same(x) for x in xs)) != 1:
+            return None
+        if self.branches_are_scales:
+            return tuple(self._trunk.prefix(self.features, x)[0] for x in xs)
+        if cache:                              # P.train_prefix_cache: rows of a resident set are looked up, not recomputed (_SplitTrunk.prefix_cached)
+            got = self._trunk.prefix_cached(self.features, xs)
+            if got is not None:
+                return got
+        if len(xs) == 1:                       # no torch.cat: it would add a copy of the whole batch to every step
+            return (self._trunk.prefix(self.features, xs[0])[0],)
+        sizes = [x.size(0) for x in xs]
+        f, _ = self._trunk.prefix(self.features, torch.cat(xs, 0))
+        return tuple(f.split(sizes, 0))
+
+    def suffix_engine(self):
+        """The libisx engine of the trainable trunk suffix when a training step may drive it directly (whole-slice forward / backward with
+        per-micro-batch gradients, utils/train_general._Stepper), else None."""
+        if not (self.trunk_precomputable() and SUFFIX_ENGINE and self._trunk.folded is not None):
+            return None
+        mods = list(self.features)[self._trunk.split:]
+        if not mods or not any(p.requires_grad for m in mods for p in m.parameters()):
+            return None
+        from isx.suffix import SuffixEngine
+        eng = _SplitTrunk._engine_of(self.features, self._trunk.split, mods)
+        return eng if eng and SuffixEngine.applicable(mods) else None
+
+    def _tail_engine(self, switch, slot, engine_class):
+        """The gate of head_engine / classif_head_engine: the engine of everything behind the trunk for all local micro-batches of a training
+        step at once, when the step may drive it by hand -- its A/B switch on, GPU training with a precomputable trunk whose trainable part
+        (if any) runs on the suffix engine, a tail the engine class takes.  The instance is cached on the net (`slot` of its __dict__) and
+        rebuilt when the modules it captured were replaced (engine.built_for)."""
+        if not (switch and self.trunk_precomputable() and self._trunk.folded is not None):
+            return None
+        mods = list(self.features)[self._trunk.split:]
+        if any(p.requires_grad for m in mods for p in m.parameters()) and self.suffix_engine() is None:
+            return None
+        if not engine_class.applicable(self):
+            return None
+        eng = self.__dict__.get(slot)
+        if eng is None or not eng.built_for(self):
+            eng = self.__dict__[slot] = engine_class(self)
+        return eng
+
+    def head_engine(self):
+        return None
+
+    def classif_head_engine(self):
+        return None
+
+
+class TuneClassif(TrunkHooks):
     def __init__(self, net, num_classes, untrained=-1, reduc=True):
         super().__init__()
         self.features, self.feature_reduc, self.classifier = extract_layers(net)
@@ -105,67 +182,20 @@ class TuneClassif(nn.Module):
 
     def forward(self, x):
         if self.training and torch.is_grad_enabled() and x.is_cuda:
-            x = self._split_trunk()(self.features, x)          # fine-tuning on the GPU: frozen prefix on the folded HIP trunk (_SplitTrunk)
+            x = self._trunk(self.features, x)          # fine-tuning on the GPU: frozen prefix on the folded HIP trunk (_SplitTrunk)
         else:
             x = self.features(x)
         x = self.feature_reduc(x)
         return self.classifier(x.reshape(x.size(0), -1))     # logical (C,h,w) order whatever the memory format
 
-    # ---- hooks of the training step (utils/train_general._Stepper), one branch: what DescriptorNet offers for its three ------------------
-    def _split_trunk(self):
-        t = self.__dict__.get('_trunk')
-        if t is None:
-            t = self.__dict__['_trunk'] = _SplitTrunk()
-        return t
-
-    def trunk_precomputable(self):
-        """True when precompute_trunk can serve training steps: training mode, GPU, a frozen trunk prefix, BatchNorm not learning."""
-        p = next(self.features.parameters(), None)
-        return bool(self.training and p is not None and p.is_cuda and _SplitTrunk.enabled(self.features))
-
-    def precompute_trunk(self, x, cache=False):
-        """The frozen trunk prefix of a whole image batch in one launch of the folded inference trunk (see DescriptorNet.precompute_trunk);
-        None when the trunk has to run inside the step (nothing frozen, BatchNorm learning, CPU tensors, eval mode)."""
-        trunk = self._split_trunk()
-        if not self.training or not (x.is_cuda and x.dtype == torch.float32) or not trunk.usable(self.features, x):
-            return None
-        if cache:
-            got = trunk.prefix_cached(self.features, (x,))
-            if got is not None:
-                return got
-        f, _ = trunk.prefix(self.features, x)
-        return (f,)
-
-    def suffix_engine(self):
-        """The libisx engine of the trainable trunk suffix when a training step may drive it directly, else None (DescriptorNet.suffix_engine)."""
-        trunk = self._split_trunk()
-        if not (self.trunk_precomputable() and SUFFIX_ENGINE and trunk.folded is not None):
-            return None
-        mods = list(self.features)[trunk.split:]
-        if not mods or not any(p.requires_grad for m in mods for p in m.parameters()):
-            return None
-        from isx.suffix import SuffixEngine
-        eng = _SplitTrunk._engine_of(self.features, trunk.split, mods)
-        return eng if eng and SuffixEngine.applicable(mods) else None
-
+    # ---- hooks of the training step (utils/train_general._Stepper), one branch; the rest are TrunkHooks' --------------------------------------
     def classif_head_engine(self):
         """The libisx engine of pool -> classifier -> cross-entropy for all local micro-batches of a training step at once (isx/classif_head.py),
         when the step may drive it by hand: a single classifier layer behind a single average pool (the ResNets; TuneClassifSub: the box pool
         and the 1x1 classifier over the windows of one scale), GPU training with a precomputable trunk whose trainable part (if any) runs on
         the suffix engine.  ISX_CLASSIF_ENGINE=0: None (the tail stays on torch autograd)."""
-        trunk = self._split_trunk()
-        if not (CLASSIF_ENGINE and self.trunk_precomputable() and trunk.folded is not None):
-            return None
-        mods = list(self.features)[trunk.split:]
-        if any(p.requires_grad for m in mods for p in m.parameters()) and self.suffix_engine() is None:
-            return None
         from isx.classif_head import ClassifHeadEngine
-        if not ClassifHeadEngine.applicable(self):
-            return None
-        eng = self.__dict__.get("_classif_head_engine")
-        if eng is None or eng.cls is not self.classifier[0] or eng.pool is not self.feature_reduc[0]:
-            eng = self.__dict__["_classif_head_engine"] = ClassifHeadEngine(self)
-        return eng
+        return self._tail_engine(CLASSIF_ENGINE, "_classif_head_engine", ClassifHeadEngine)
 
     def head_rows(self, f, n_branches=1):
         """pool + classifier on the trunk output of one branch (torch autograd when f carries a graph): the class scores"""
@@ -174,7 +204,7 @@ class TuneClassif(nn.Module):
 
     def forward_features(self, f):
         """forward() of training mode on precomputed prefix features: trainable suffix + pool + classifier"""
-        return self.head_rows(_SplitTrunk.suffix(self.features, f, self._split_trunk().split))
+        return self.head_rows(_SplitTrunk.suffix(self.features, f, self._trunk.split))
 
 
 class TuneClassifSub(TuneClassif):
@@ -189,32 +219,21 @@ class TuneClassifSub(TuneClassif):
 
     def forward_single(self, x):
         if self.training and torch.is_grad_enabled() and x.is_cuda:
-            return self.head_rows(self._split_trunk()(self.features, x))     # training on the GPU: frozen prefix on the folded HIP trunk (_SplitTrunk)
+            return self.head_rows(self._trunk(self.features, x))     # training on the GPU: frozen prefix on the folded HIP trunk (_SplitTrunk)
         return self.classifier(self.feature_reduc(self.features(x)))
 
     def forward(self, *scales):
         return [self.forward_single(x) for x in scales]
 
     # ---- hooks of the training step (utils/train_general._Stepper._classif_batched): one branch PER SCALE of an image, each of its own spatial
-    # size (train/classif_regions.py).  trunk_precomputable, suffix_engine and classif_head_engine are TuneClassif's. --------------------------
-    def precompute_trunk(self, *scales, cache=False):
-        """The frozen trunk prefix of every scale's image batch, one launch of the folded inference trunk PER SCALE (the scales differ in size):
-        a tuple of feature tensors of different spatial size, or None when the trunk has to run inside the step (see TuneClassif).  The
-        prefix-feature table of a resident set (`cache`) holds one size only: not used here."""
-        trunk = self._split_trunk()
-        if not self.training or not scales or not all(x.is_cuda and x.dtype == torch.float32 for x in scales):
-            return None
-        if not trunk.usable(self.features, scales[0]) or len(set(x.size(0) for x in scales)) != 1:
-            return None
-        return tuple(trunk.prefix(self.features, x)[0] for x in scales)
-
+    # size (train/classif_regions.py).  precompute_trunk (one launch per scale), suffix_engine and classif_head_engine are inherited. ----------
     def head_rows(self, f, n_branches=1):
         """box pool + convolutionalised classifier on the trunk output of one scale (torch autograd when f carries a graph): the class-score map"""
         return self.classifier(self.feature_reduc(f))
 
     def forward_features(self, *feats):
         """forward() of training mode on precomputed prefix features: trainable suffix + pool + classifier, scale by scale"""
-        split = self._split_trunk().split
+        split = self._trunk.split
         return [self.head_rows(_SplitTrunk.suffix(self.features, f, split)) for f in feats]
 
 
@@ -270,15 +289,19 @@ class _SplitTrunk(object):
         with torch.no_grad():
             return self.folded(x.contiguous(memory_format=torch.channels_last)), split
 
+    @staticmethod
+    def _key(features, x, split, mods):
+        """A folded copy of `mods` (the modules of `features` on one side of `split`) is stale as soon as any of their weights or BN buffers is
+        written in place (load_state_dict) or replaced, or the split moves: identity + version counter of every such tensor are the key (no
+        state_dict() is built per call; writes through `.data` bypass the counters -- set `self.folded = None` after such surgery)."""
+        return (id(features), str(x.device), split,
+                tuple((id(t), t._version) for m in mods for t in m.parameters()), tuple((id(t), t._version) for m in mods for t in m.buffers()))
+
     def _refresh(self, features, x):
         """(Re)build the folded prefix when its weights / buffers / split changed; returns the split index."""
         split = first_trainable(features)
         mods = list(features)[:split]
-        # the folded copy is stale as soon as any weight or BN buffer of the prefix is written in place (load_state_dict) or replaced, or
-        # the split moves: identity + version counter of every prefix tensor are the key (no state_dict() is built per call; writes
-        # through `.data` bypass the counters -- set `self.folded = None` after such surgery)
-        key = (id(features), str(x.device), split,
-               tuple((id(t), t._version) for m in mods for t in m.parameters()), tuple((id(t), t._version) for m in mods for t in m.buffers()))
+        key = self._key(features, x, split, mods)
         if self.folded is None or self.key != key:
             from .nn_utils import fold_batch_norm
             self.folded = fold_batch_norm(nn.Sequential(*mods)).to(x.device).to(memory_format=torch.channels_last)
@@ -367,8 +390,7 @@ class _SplitTrunk(object):
         mods = list(features)[split:]
         if not mods:
             return f
-        key = (id(features), str(x.device), split,
-               tuple((id(t), t._version) for m in mods for t in m.parameters()), tuple((id(t), t._version) for m in mods for t in m.buffers()))
+        key = self._key(features, x, split, mods)
         if getattr(self, "_tail", None) is None or self._tail[0] != key:
             from .nn_utils import fold_batch_norm
             self._tail = (key, fold_batch_norm(nn.Sequential(*mods)).to(x.device).to(memory_format=torch.channels_last))
@@ -492,7 +514,7 @@ def _box_pools(reduc):
             m.__class__ = BoxPool
 
 
-class DescriptorNet(nn.Module):
+class DescriptorNet(TrunkHooks):
     def __init__(self, net, feature_dim, feature_size2d, untrained=-1):
         super().__init__()
         self.features, _, classifier = extract_layers(net)
@@ -501,68 +523,19 @@ class DescriptorNet(nn.Module):
         self.feature_size = feature_dim if feature_dim > 0 else get_feature_size(classifier)
         self.feature_reduc1 = _descriptor_head(in_features, self.feature_size)
         self.feature_reduc2 = NormalizeL2()
-        self._trunk = _SplitTrunk()
 
     def forward_single(self, x):
-        x = self._trunk(self.features, x) if self.training else self._trunk.inference(self.features, x)
-        x = x.reshape(x.size(0), -1)
-        return self.feature_reduc2(_apply_head(self.feature_reduc1, x))
+        return self._head_only(self._trunk(self.features, x) if self.training else self._trunk.inference(self.features, x))
 
     def _tail_and_head(self, f):
         """trainable trunk suffix + descriptor head + final L2 on PREFIX features (B, C, h, w) that were computed elsewhere"""
-        f = _SplitTrunk.suffix(self.features, f, self._trunk.split)
-        return self.feature_reduc2(_apply_head(self.feature_reduc1, f.reshape(f.size(0), -1)))
-
-    def trunk_precomputable(self):
-        """True when precompute_trunk can serve training steps: training mode, GPU, a frozen trunk prefix, BatchNorm not learning."""
-        p = next(self.features.parameters(), None)
-        return bool(self.training and p is not None and p.is_cuda and _SplitTrunk.enabled(self.features))
-
-    def precompute_trunk(self, *xs, cache=False):
-        """Training with a frozen trunk PREFIX and frozen BatchNorm (the reference's configurations: stem + layers 1-3 frozen, layer4
-        trained; or everything frozen with untrained = -1): the prefix output of an image does not depend on the batch it rides in and needs
-        no autograd graph, so the prefix of a whole mini-batch runs as ONE launch of the folded inference trunk instead of once per
-        micro-batch of 8 triplets (24 images: far too few to fill the chip).  Returns the prefix feature tensors of the given image batches
-        (same split), or None when the trunk has to run inside the step (nothing frozen, BatchNorm learning, CPU tensors, eval mode)."""
-        if not self.training or not xs or not all(x.is_cuda and x.dtype == torch.float32 for x in xs):
-            return None
-        if not self._trunk.usable(self.features, xs[0]) or len(set(tuple(x.shape[1:]) for x in xs)) != 1:
-            return None
-        if cache:                              # P.train_prefix_cache: rows of a resident set are looked up, not recomputed (_SplitTrunk.prefix_cached)
-            got = self._trunk.prefix_cached(self.features, xs)
-            if got is not None:
-                return got
-        sizes = [x.size(0) for x in xs]
-        f, _ = self._trunk.prefix(self.features, torch.cat(xs, 0))
-        return tuple(f.split(sizes, 0))
-
-    def suffix_engine(self):
-        """The libisx engine of the trainable trunk suffix when a training step may drive it directly (whole-slice forward / backward with
-        per-micro-batch gradients, utils/train_general._Stepper), else None."""
-        if not (self.trunk_precomputable() and SUFFIX_ENGINE and self._trunk.folded is not None):
-            return None
-        mods = list(self.features)[self._trunk.split:]
-        if not mods or not any(p.requires_grad for m in mods for p in m.parameters()):
-            return None
-        from isx.suffix import SuffixEngine
-        eng = _SplitTrunk._engine_of(self.features, self._trunk.split, mods)
-        return eng if eng and SuffixEngine.applicable(mods) else None
+        return self._head_only(_SplitTrunk.suffix(self.features, f, self._trunk.split))
 
     def head_engine(self):
         """The libisx engine of the descriptor head for all local micro-batches of a training step at once (isx/head.py), when the step may
         drive it by hand: GPU training with a precomputable trunk whose trainable part (if any) runs on the suffix engine."""
-        if not (HEAD_ENGINE and self.trunk_precomputable() and self._trunk.folded is not None):
-            return None
-        mods = list(self.features)[self._trunk.split:]
-        if any(p.requires_grad for m in mods for p in m.parameters()) and self.suffix_engine() is None:
-            return None
         from isx.head import HeadEngine
-        if not HeadEngine.applicable(self):
-            return None
-        eng = self.__dict__.get("_head_engine")
-        if eng is None or eng.lin is not self.feature_reduc1[2] or eng.shift is not self.feature_reduc1[1]:
-            eng = self.__dict__["_head_engine"] = HeadEngine(self)
-        return eng
+        return self._tail_engine(HEAD_ENGINE, "_head_engine", HeadEngine)
 
     def head_features(self, f1, f2=None, f3=None):
         """descriptor head + final L2 on the SUFFIX output of the branches (together, as forward_features sends them through suffix + head)"""

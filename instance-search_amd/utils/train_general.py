@@ -100,7 +100,10 @@ class _Stepper(object):
     def __init__(self, P, net, make_batch, make_loss):
         from isx import dp
         from model.custom_modules import RowDeferredLinear
+        from model.siamese import TrunkHooks
         self.P, self.net, self.make_batch, self.make_loss = P, net, make_batch, make_loss
+        # a net without the training step's hooks (RegionDescriptorNet, any plain nn.Module) takes the generic per-micro-batch route
+        self.hooked = isinstance(net, TrunkHooks)
         self.rank, self.world = _dp()
         mode = getattr(P, 'train_grad_exchange', 'tree')
         if mode not in ('tree', 'allreduce'):
@@ -174,19 +177,39 @@ class _Stepper(object):
         obj.backward()
         return obj.detach().reshape(-1)[0]           # a device scalar: the step reads the running loss back once, not per micro-batch
 
+    def _prefix_ok(self, n_leaves):
+        """May the frozen trunk prefix be computed outside the micro-batches this step?"""
+        return bool(self.hooked and getattr(self.P, 'train_trunk_per_minibatch', True) and n_leaves >= 1 and self.net.trunk_precomputable())
+
     def _precompute(self, local, n_leaves, batch_args):
         """Frozen trunk prefix: ONE batch construction for the whole local slice (same image order as micro-batch by micro-batch) and one
         prefix launch; the micro-batches then run suffix + head on their rows of the features."""
-        if not (getattr(self.P, 'train_trunk_per_minibatch', True) and n_leaves >= 1 and getattr(self.net, 'trunk_precomputable', lambda: False)()):
+        if not self._prefix_ok(n_leaves):
             return None
         rng_state = random.getstate()
         inputs, targets = self.make_batch(local, len(local), **batch_args)
-        feats = (self.net.precompute_trunk(*inputs, cache=True) if getattr(self.P, 'train_prefix_cache', False)
-                 else self.net.precompute_trunk(*inputs))
+        feats = self.net.precompute_trunk(*inputs, cache=bool(getattr(self.P, 'train_prefix_cache', False)))
         if feats is None:                            # (CPU tensors, ragged shapes): the batch is built again per micro-batch, from the same random state
             random.setstate(rng_state)
             return None
         return feats, targets
+
+    def _flat_all(self, L):
+        return self.flat.flat.new_zeros((L, self.flat.flat.numel()))                 # one zeroed flat gradient row per leaf
+
+    @staticmethod
+    def _suffix_forward(eng, feats, offsets, k):
+        """The k rows of every leaf of every branch in `feats`, leaf-major ([a_0; p_0; n_0; a_1; ...]), through the trunk suffix."""
+        with _phase("suffix_forward"):
+            x_all = torch.cat([f[o:o + k] for o in offsets for f in feats], 0)
+            if eng is not None:
+                return eng.forward(x_all)                                            # no graph: the engine's backward is driven by hand
+            return x_all, None                                                       # the whole trunk is frozen: nothing to train below the head
+
+    def _suffix_backward(self, eng, saved, dy_all, L, flat_all):
+        if eng is not None:
+            with _phase("suffix_backward"):
+                eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
 
     def _leaves_batched(self, eng, head, mine, offsets, mini_size, pre, sink):
         """All local micro-batches through the trainable trunk suffix (isx/suffix.py) and -- when `head` is given -- the descriptor head
@@ -201,13 +224,8 @@ class _Stepper(object):
         rows = nb * k
         share = k / float(mini_size)
         flat = self.flat.flat
-        flat_all = torch.zeros((L, flat.numel()), dtype=flat.dtype, device=flat.device)
-        with _phase("suffix_forward"):
-            x_all = torch.cat([f[o:o + k] for o in offsets for f in feats], 0)      # leaf-major: [a_0; p_0; n_0; a_1; ...]
-            if eng is not None:
-                y_all, saved = eng.forward(x_all)                                    # no graph: the engine's backward is driven by hand below
-            else:
-                y_all, saved = x_all, None                                           # the whole trunk is frozen: nothing to train below the head
+        flat_all = self._flat_all(L)
+        y_all, saved = self._suffix_forward(eng, feats, offsets, k)
         losses = []
 
         def leaf_grads(out_of, x_all):
@@ -248,9 +266,7 @@ class _Stepper(object):
                 else:
                     dd = leaf_grads(lambda d: _SplitRows.apply(d, nb), d_all)
                 dy_all = head.backward(hctx, dd, L, sink, flat_all, self.flat.slices)
-        if eng is not None:
-            with _phase("suffix_backward"):
-                eng.backward(saved, dy_all, leaves=L, leaf_grads=(flat_all, self.flat.slices))
+        self._suffix_backward(eng, saved, dy_all, L, flat_all)
         return flat_all, losses
 
     @staticmethod
@@ -280,26 +296,42 @@ class _Stepper(object):
         and what a rank of a P-rank run computes.  A leaf's loss is summed over the scales the same way.  Returns (flat_all (L, total), losses)."""
         feats, targets_all = pre
         k, L, S = len(mine[0]), len(mine), len(feats)
-        flat = self.flat.flat
-        flat_all = torch.zeros((L, flat.numel()), dtype=flat.dtype, device=flat.device)
+        flat_all = self._flat_all(L)
         labels = torch.cat([targets_all[0][o:o + k] for o in offsets], 0)
         total = None
         for s, f in enumerate(feats):
             part = flat_all if s == 0 else torch.zeros_like(flat_all)
-            with _phase("suffix_forward"):
-                x_all = torch.cat([f[o:o + k] for o in offsets], 0)
-                y_all, saved = eng.forward(x_all) if eng is not None else (x_all, None)
+            y_all, saved = self._suffix_forward(eng, (f,), offsets, k)
             # the leaf's window rows at this scale; its share of the mini-batch, the scales averaged
             scale_a, scale_b, rescale = self._leaf_scales(xent, k * chead.rows_per_image(y_all.shape[2], y_all.shape[3]), k / float(mini_size) / S)
             with _phase("heads"):
                 per_leaf, dy_all = chead.step(y_all, labels, L, scale_a, scale_b, part, self.flat.slices, need_dy=eng is not None)
                 total = rescale(per_leaf) if total is None else total + rescale(per_leaf)
-            if eng is not None:
-                with _phase("suffix_backward"):
-                    eng.backward(saved, dy_all, leaves=L, leaf_grads=(part, self.flat.slices))
+            self._suffix_backward(eng, saved, dy_all, L, part)
             if s > 0:
                 flat_all += part
         return flat_all, list(total.unbind(0))
+
+    def _route(self, mine, n, mb, pre, sink):
+        """The batched route of this step: a callable (leaves, their row offsets) -> (flat_all: one flat gradient row per leaf, losses), or
+        None for the generic route (one _forward_backward per micro-batch)."""
+        # batched engines need equal micro-batches; decided from the MINI-BATCH (n % mb == 0: every leaf of every rank has mb triplets), not from
+        # this rank's leaves, so that every rank and the single-process run take the same numeric path (round-4 ADVICE)
+        if not (self.hooked and self.mode == 'tree' and pre is not None and mine and n % mb == 0):
+            return None
+        # a net whose branches are the SCALES of an image (TuneClassifSub: feature maps of different size per branch) takes the
+        # classifier route or the generic one, never _leaves_batched (which stacks the branches)
+        scales = self.net.branches_are_scales
+        xent = getattr(self.make_loss, 'region_cross_entropy' if scales else 'cross_entropy', None)
+        chead = self.net.classif_head_engine() if xent is not None else None
+        if chead is None and scales:
+            return None
+        eng, head = self.net.suffix_engine(), self.net.head_engine()
+        if chead is not None and self._scales_fit(eng, chead, pre[0], mb):
+            return lambda m, o: self._classif_batched(eng, chead, xent, m, o, n, pre)
+        if not scales and (eng is not None or head is not None):
+            return lambda m, o: self._leaves_batched(eng, head, m, o, n, pre, sink)
+        return None
 
     def _slice(self, mini_batch):
         """This rank's micro-batches of a mini-batch: (leaves, first leaf index, one past the last, their items in order, row offset of each leaf)."""
@@ -334,9 +366,8 @@ class _Stepper(object):
         G = int(getattr(P, 'train_prefix_ahead', 8))
         G = G * self.world if G > 1 else G
         ds = getattr(self, '_epoch_set', None)
-        if (G < 2 or ds is None or start is None or n_leaves < 1 or not getattr(self.make_batch, 'deterministic', False)
-                or getattr(P, 'train_prefix_cache', False) or not getattr(P, 'train_trunk_per_minibatch', True)
-                or not getattr(self.net, 'trunk_precomputable', lambda: False)()):
+        if (G < 2 or ds is None or start is None or not getattr(self.make_batch, 'deterministic', False)
+                or getattr(P, 'train_prefix_cache', False) or not self._prefix_ok(n_leaves)):
             return None
         a = self._ahead
         if a is None or not (a[0] <= start < a[0] + a[1] * n) or (start - a[0]) % n:
@@ -384,22 +415,7 @@ class _Stepper(object):
                 sh.begin_step(len(mine))
             sink.leaf_ids = list(range(lo, hi))
             batched = getattr(P, 'train_suffix_batched', True)
-            # batched engines need equal micro-batches; decided from the MINI-BATCH (n % mb == 0: every leaf of every rank has mb triplets), not from
-            # this rank's leaves, so that every rank and the single-process run take the same numeric path (round-4 ADVICE)
-            route = None                              # (leaves, their row offsets) -> (flat_all: one flat gradient row per leaf, losses)
-            if self.mode == 'tree' and pre is not None and mine and n % mb == 0 and batched:
-                # a net whose branches are the SCALES of an image (TuneClassifSub: feature maps of different size per branch) takes the
-                # classifier route or the generic one, never _leaves_batched (which stacks the branches)
-                scales = getattr(self.net, 'branches_are_scales', False)
-                xent = getattr(self.make_loss, 'region_cross_entropy' if scales else 'cross_entropy', None)
-                chead = getattr(self.net, 'classif_head_engine', lambda: None)() if xent is not None else None
-                if chead is not None or not scales:
-                    eng = getattr(self.net, 'suffix_engine', lambda: None)()
-                    head = getattr(self.net, 'head_engine', lambda: None)()
-                    if chead is not None and self._scales_fit(eng, chead, pre[0], mb):
-                        route = lambda m, o: self._classif_batched(eng, chead, xent, m, o, n, pre)
-                    elif not scales and (eng is not None or head is not None):
-                        route = lambda m, o: self._leaves_batched(eng, head, m, o, n, pre, sink)
+            route = self._route(mine, n, mb, pre, sink) if batched else None
             flat_all = None
             if route is not None and batched == "leaf":  # test mode: the same machinery one micro-batch at a time (what a rank with ONE leaf runs)
                 parts = [route([mine[j]], [offsets[j]]) for j in range(len(mine))]

@@ -242,7 +242,7 @@ def test_engine_step_matches_float64_autograd_and_the_autograd_tail(monkeypatch)
     # float64 autograd on the same prefix features with the engine's ReLU pattern pinned
     net.load_state_dict(start)
     (f,) = net.precompute_trunk(x)
-    split = net._split_trunk().split
+    split = net._trunk.split
     eng = net.suffix_engine()
     _, saved = eng.forward(f)
     masks = [tuple((t > 0).permute(0, 3, 1, 2).double() for t in (t1, t2, yb)) for _, t1, t2, yb in saved]

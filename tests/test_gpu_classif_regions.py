@@ -197,7 +197,7 @@ def test_scales_step_matches_float64_autograd_and_the_autograd_tail(setup, monke
     net.load_state_dict(start)
     feats = net.precompute_trunk(*xs)
     assert [tuple(f.shape[2:]) for f in feats] == [(18, 18), (14, 14)]
-    split = net._split_trunk().split
+    split = net._trunk.split
     eng = net.suffix_engine()
     blocks64 = copy.deepcopy(nn.Sequential(*list(net.features)[split:])).double()
     conv64 = copy.deepcopy(net.classifier[0]).double()

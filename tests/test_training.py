@@ -313,6 +313,43 @@ def test_region_training_runs_and_learns_on_cpu():
     assert score >= 0 and any(p.grad is not None and float(p.grad.abs().sum()) > 0 for p in net.parameters() if p.requires_grad)
 
 
+def test_stepper_takes_the_generic_route_for_a_net_without_the_hooks():
+    """The training step's contract is a class (model/siamese.TrunkHooks), not a set of method names: a net outside it -- RegionDescriptorNet,
+    any plain module, here one whose like-named methods must never be called -- gets no prefix, no batched route and one batch construction
+    + forward + backward per micro-batch."""
+    from model.custom_modules import TripletLoss
+    from model.siamese import RegionDescriptorNet, TrunkHooks
+    from train.params import Params
+    from utils.train_general import _Stepper, make_sgd
+    assert not issubclass(RegionDescriptorNet, TrunkHooks)
+
+    class NotAsked(_TinyNet):
+        def _never(self, *a, **k):
+            raise AssertionError("a hook of a net outside the contract was called")
+        trunk_precomputable = precompute_trunk = suffix_engine = head_engine = classif_head_engine = forward_features = _never
+
+    torch.manual_seed(0)
+    net = NotAsked().train()
+    x = torch.randn(4, 3, 8, 8)
+    built = []
+
+    def make_batch(items, n):
+        built.append(list(items))
+        idx = torch.tensor(items)
+        return [x[idx], x[idx.flip(0)], x[(idx + 1) % 4]], []
+
+    crit = TripletLoss(0.1, False, True)
+    P = Params(cuda_device=-1, train_batch_size=4, train_micro_batch=2, train_loss_avg=False)
+    stepper = _Stepper(P, net, make_batch, lambda out, targets: (crit(*out), None))
+    assert stepper.hooked is False and not stepper._prefix_ok(2)
+    assert stepper._route([[0, 1], [2, 3]], 4, 2, ((x,), []), None) is None          # not even with prefix features in hand
+    opt = make_sgd((p for p in net.parameters() if p.requires_grad), 1e-2, 0.0, 0.0)
+    before = net.head.weight.detach().clone()
+    loss = stepper.step(opt, [0, 1, 2, 3], {})
+    assert built == [[0, 1], [2, 3]] and float(loss) > 0
+    assert not torch.equal(net.head.weight.detach(), before)
+
+
 def test_grad_all_reducer_single_process_is_noop():
     from isx.dp import GradAllReducer
     net = _TinyNet()
