@@ -121,6 +121,18 @@ int isx_conv3x3_expand_nhwc(const float* x, int64_t B, int H, int W, int Cin, co
 int isx_conv3x3_expand_dual_nhwc(const float* t, int64_t B, int H, int W, int Cin, const float* w2_ohwi, const float* b2, const float* x2,
                                  const float* wcat_t, int Cout, const float* bias, int relu, float* y, isx_stream_t stream);
 
+/* conv2 + conv3 of an identity Bottleneck with 128 mid channels (layer2[1..3] of the ResNet-50 trunk; BN folded) as ONE kernel:
+ *   y = act( W3 . relu(conv3x3(x, W2) + b2) + b3 + (residual ? residual : 0) ),     3x3: padding 1, stride 1.
+ * The 128-channel mid activation stays on chip: a workgroup's 128 x 128 accumulator tile of the 3x3 convolution goes registers -> LDS and is the A
+ * operand of every 128-column tile of the expansion.  Same sums as isx_conv3x3_nhwc followed by isx_conv1x1_nhwc (two-level, ISX_CONV_CHUNK; the
+ * expansion: chain over mid channels 0-63, chain over 64-127, added in order): bit-identical results.
+ * x: (B,H,W,Cin), Cin % 64 == 0; w2_ohwi: (128,3,3,Cin); b2: (128); w3t: (128,Cout) = the 1x1 weight (Cout,128) TRANSPOSED; b3: (Cout);
+ * y / residual: (B,H,W,Cout), Cout % 128 == 0, Cout <= 2^20.  x, w2_ohwi and w3t 16-B aligned; y must not alias x or residual.  B == 0 is a no-op.
+ * Row order as isx_conv3x3_nhwc: position-major (padding taps skipped) for B >= 128 on maps up to 28x28, pixel-major otherwise -- the two orders
+ * agree for FINITE weights (a non-finite weight under a padding tap gives NaN pixel-major and is skipped position-major). */
+int isx_conv3x3_expand128_nhwc(const float* x, int64_t B, int H, int W, int Cin, const float* w2_ohwi, const float* b2, const float* w3t, int Cout,
+                               const float* b3, const float* residual, int relu, float* y, isx_stream_t stream);
+
 /* The whole stem as ONE kernel: conv 7x7 / stride 2 / padding 3 (3 -> 64 channels, bn1 folded into w and bias) + ReLU +
  * MaxPool2d(3, stride 2, padding 1) on a channels-last image batch; the convolution output never reaches memory.  Replaces
  * conv1, bn1, relu, maxpool of the torchvision ResNet `features` trunk (model/ModelDefinition.py, split by model/nn_utils.py:56-71,

@@ -245,6 +245,15 @@ static std::atomic<int> g_pos_major{[] { const char* e = getenv("ISX_DEBUG_CONV_
 // at 28x28.  56x56 outputs (the Cin = 64 layers: 64x64 tiles or the fused expand kernel) have 1.2 % padding and stay pixel-major.
 constexpr int kPosMajorMaxP = 28 * 28;
 
+// Virtual row count of a 3x3 launch in the position-major row order, 0 = the shape stays pixel-major (isx_conv3x3_nhwc and the fused
+// isx_conv3x3_expand128_nhwc, expand.hip).  Cout: channels of a row of y (the fused kernel: of the expansion's output); tiles_n64: 64-column n-tiles.
+int64_t conv3x3_pos_major_rows(int64_t B, int H, int W, int Cin, int Ho, int Wo, int64_t Cout, int64_t tiles_n64) {
+    const int64_t P = (int64_t)Ho * Wo;
+    const bool pos_major = g_pos_major && Cin % kConvChunk == 0 && B >= 128 && P <= kPosMajorMaxP &&
+                           (128ll * H * W + 2 * W + 4) * Cin * 4 < (1ll << 32) && 128ll * P * Cout * 4 < (1ll << 31);
+    return pos_major && ((B + 127) / 128 * P * 2) * tiles_n64 < (1ll << 31) ? (B + 127) / 128 * P * 128 : 0;        // (tile count of the virtual rows)
+}
+
 // steady-state efficiency of the 3x3 tile shapes (128x128, -, 128x64, 64x64) for pick_tile_cfg: forward and input gradient
 static const float kEff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
 
@@ -292,10 +301,7 @@ ISX_API int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, c
     // Position-major row order (conv3x3_tile.hpp: the k loop skips the padding taps) for the 128x128 tiles and their 64x64 tails:
     // whole chunks of the two-level sum per tap, groups of 128 images that are not mostly empty, small maps, and 128 rows of x (H W Cin floats
     // apart, plus the taps) / of y (P Cout floats apart) inside the 32-bit offsets of a buffer descriptor.  The tile model then sees the virtual rows.
-    const int64_t P = (int64_t)g.Ho * g.Wo;
-    const bool pos_major = g_pos_major && Cin % kConvChunk == 0 && B >= 128 && P <= kPosMajorMaxP &&
-                           (128ll * H * W + 2 * W + 4) * Cin * 4 < (1ll << 32) && 128ll * P * Cout * 4 < (1ll << 31);
-    const int64_t Mv = pos_major && ((B + 127) / 128 * P * 2) * ((N + 63) / 64) < (1ll << 31) ? (B + 127) / 128 * P * 128 : 0;        // (tile count of the virtual rows)
+    const int64_t Mv = conv3x3_pos_major_rows(B, H, W, Cin, g.Ho, g.Wo, Cout, (N + 63) / 64);
     const int64_t Ms = Mv > 0 ? Mv : M;
     int best = pick_tile_cfg(Ms, N, gemm_tail_split_rows(Ms, N, 256 * kWgPerCu128), kEff3x3, 0xD, kWgPerCu128);
     { const int fc_ = g_force_conv_cfg; if (fc_ == 0 || fc_ == 2 || fc_ == 3) best = fc_; }

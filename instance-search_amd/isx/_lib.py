@@ -31,6 +31,7 @@ _SIGNATURES = {
     "isx_stem7x7_pool_nhwc": (C.c_int, [VP, I64, I32, I32, VP, VP, VP, VP]),
     "isx_conv3x3_expand_nhwc": (C.c_int, [VP, I64, I32, I32, I32, VP, VP, I32, VP, I32, VP, VP, I32, VP, VP]),
     "isx_conv3x3_expand_dual_nhwc": (C.c_int, [VP, I64, I32, I32, I32, VP, VP, VP, VP, I32, VP, I32, VP, VP]),
+    "isx_conv3x3_expand128_nhwc": (C.c_int, [VP, I64, I32, I32, I32, VP, VP, VP, I32, VP, VP, I32, VP, VP]),
     "isx_conv3x3_nhwc": (C.c_int, [VP, I64, I32, I32, I32, VP, I32, I32, VP, VP, I32, VP, VP]),
     "isx_boxpool_s1": (C.c_int, [VP, I64, I32, I32, I32, I32, I32, VP, VP]),
     "isx_boxpool_s1_nhwc": (C.c_int, [VP, I64, I32, I32, I32, I32, I32, VP, VP]),

@@ -357,6 +357,37 @@ def conv3x3_expand_nhwc(x, w2_ohwi, b2, stride, w3t, b3, residual=None, relu=Tru
     return y
 
 
+def conv3x3_expand128_nhwc(x, w2_ohwi, b2, w3t, b3, residual=None, relu=True):
+    """conv2 + conv3 of an identity Bottleneck with 128 mid channels as ONE kernel: act(W3 . relu(conv3x3(x, W2) + b2) + b3 (+ residual)), stride 1.
+    x: channels-last (B,Cin,H,W), Cin % 64 == 0; w2_ohwi: (128,3,3,Cin); w3t: (128,Cout) = conv3.weight.view(Cout,128).t().contiguous(),
+    Cout % 128 == 0.  Returns channels-last (B,Cout,H,W)."""
+    if not (x.dtype == torch.float32 and x.dim() == 4):
+        raise _lib.IsxError("x must be a channels-last float32 CUDA tensor (B,C,H,W)")
+    B, Cin, H, W = x.shape
+    if tuple(w2_ohwi.shape) != (128, 3, 3, Cin) or w3t.dim() != 2 or w3t.shape[0] != 128:
+        raise _lib.IsxError("w2_ohwi must be (128, 3, 3, Cin) and w3t (128, Cout)")
+    Cout = w3t.shape[1]
+    if Cin % 64 != 0 or Cout % 128 != 0:
+        raise _lib.IsxError("Cin must be a multiple of 64 and Cout a multiple of 128")
+    if not (x.is_cuda and x.is_contiguous(memory_format=torch.channels_last)):
+        raise _lib.IsxError("x must be a channels-last float32 CUDA tensor (B,C,H,W)")
+    _on_current_device(x, "x")
+    w2 = _f32(w2_ohwi, "w2_ohwi")
+    w3 = _f32(w3t, "w3t")
+    y = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    rp = 0
+    if residual is not None:
+        if residual.shape != y.shape or residual.dtype != torch.float32 or not residual.is_contiguous(memory_format=torch.channels_last):
+            raise _lib.IsxError("residual must be a channels-last float32 tensor of the output's shape")
+        rp = residual.data_ptr()
+    b2p, b3p, px = _f32(b2, "b2").data_ptr(), _f32(b3, "b3").data_ptr(), B * H * W
+    _timed("isx_conv3x3_expand128_nhwc", 2.0 * px * (9 * Cin * 128 + 128 * Cout),
+           4.0 * (px * Cin + px * Cout * (2 if rp else 1) + 9 * Cin * 128 + 128 * Cout),
+           lambda: check(lib().isx_conv3x3_expand128_nhwc(x.data_ptr(), B, H, W, Cin, w2.data_ptr(), b2p, w3.data_ptr(), Cout, b3p, rp,
+                                                          1 if relu else 0, y.data_ptr(), _stream()), "isx_conv3x3_expand128_nhwc"))
+    return y
+
+
 def conv3x3_expand_dual_nhwc(t, w2_ohwi, b2, x2, wcat_t, bias, relu=True):
     """First block of a 64-mid-channel stage as ONE kernel: act([W3 | Wd] . [relu(conv3x3(t, W2) + b2) ; x2] + bias), stride 1.
     t: channels-last (B,Cin,H,W); x2: channels-last (B,64,H,W); wcat_t: (128,256) = cat([W3, Wd], 1).t().contiguous()."""

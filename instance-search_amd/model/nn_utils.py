@@ -82,7 +82,7 @@ def extract_layers(net):
 _CONV3X3_MODE = os.environ.get("ISX_CONV3X3", "auto")
 _IMPLICIT_GEMM_3X3 = _CONV3X3_MODE != "0"
 _GEMM_1X1 = os.environ.get("ISX_CONV1X1", "1") != "0"
-_FUSE_EXPAND = os.environ.get("ISX_FUSE_EXPAND", "1") != "0"     # 0: conv2 and conv3 of the 64-channel bottlenecks as two kernels again
+_FUSE_EXPAND = os.environ.get("ISX_FUSE_EXPAND", "1") != "0"     # 0: conv2 and conv3 of the 64- and 128-channel identity bottlenecks as two kernels again
 _FUSED_STEM = os.environ.get("ISX_STEM", "1") != "0"       # 0: stem convolution back to MIOpen + the separate bias/ReLU/maxpool pass
 _FUSE_PROJECTION = os.environ.get("ISX_FUSE_PROJECTION", "1") != "0"     # last 1x1 conv + projection shortcut as one GEMM
 if not (_GEMM_1X1 and _FUSED_STEM and _FUSE_EXPAND and _FUSE_PROJECTION and _CONV3X3_MODE == "auto"):
@@ -282,6 +282,16 @@ class _FusedBlock(nn.Module):
                 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
                 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
 
+    def _fusable_expand128(self, x):
+        if not (_FUSE_EXPAND and _GEMM_1X1 and _IMPLICIT_GEMM_3X3 and self.downsample is None and len(self.convs) == 3):
+            return False
+        c2, c3 = self.convs[1].conv, self.convs[2].conv
+        return (c2.kernel_size == (3, 3) and c2.padding == (1, 1) and c2.groups == 1 and c2.dilation == (1, 1) and c2.stride == (1, 1)
+                and c2.out_channels == 128 and c2.in_channels % 64 == 0 and self.convs[1].relu and self.convs[2]._pointwise() and c3.in_channels == 128
+                and c3.out_channels % 128 == 0 and x.shape[1] == c3.out_channels
+                and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
+
     def forward(self, x):
         if self._fusable_projection(x):
             # relu(conv_last(t) + projection(x) + bias) as ONE GEMM over [t ; x_strided] (libisx isx_conv1x1_dual_nhwc):
@@ -310,6 +320,15 @@ class _FusedBlock(nn.Module):
             if not t.is_contiguous(memory_format=torch.channels_last):
                 t = t.contiguous(memory_format=torch.channels_last)
             return ops.conv3x3_expand_nhwc(t, c2.w_ohwi(), c2.bias, c2.conv.stride[0], self.w3t(), c3.bias, x, c3.relu)
+        if self._fusable_expand128(x):
+            # Bottleneck with 128 mid channels and an identity shortcut (ResNet stage 2, blocks 1..): conv2 + conv3 + residual + ReLU as ONE
+            # kernel (libisx isx_conv3x3_expand128_nhwc): the 128 x 128 accumulator tile of conv2 IS the A operand of conv3
+            from isx import ops
+            c2, c3 = self.convs[1], self.convs[2]
+            t = self.convs[0](x)
+            if not t.is_contiguous(memory_format=torch.channels_last):
+                t = t.contiguous(memory_format=torch.channels_last)
+            return ops.conv3x3_expand128_nhwc(t, c2.w_ohwi(), c2.bias, self.w3t(), c3.bias, x, c3.relu)
         idt = x if self.downsample is None else self.downsample(x)
         y = x
         for c in self.convs[:-1]:

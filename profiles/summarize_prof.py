@@ -51,6 +51,8 @@ def family(name):
         return "isx_conv3x3_nhwc"
     if "conv3x3_expand_kernel" in name:
         return "isx_conv3x3_expand_nhwc"
+    if "conv3x3_expand128_kernel" in name:
+        return "isx_conv3x3_expand128_nhwc"
     if "stem7x7_pool_kernel" in name:
         return "isx_stem7x7_pool_nhwc"
     if "gap_l2_nhwc_kernel" in name or "gap_l2_kernel" in name:
