@@ -397,19 +397,28 @@ int isx_triplet_leaves(const float* d, int leaves, int k, int D, float margin, i
 
 /* ---- classification fine-tuning (pipeline stage 1, csrc/classif.hip) ----
  * Softmax cross-entropy: nn.CrossEntropyLoss of train/classif_finetune.py:154, called once per micro-batch from
- * utils/train_general.py:51-61.  logits: (B, C) fp32; labels: (B) int32 in [0, C) (an out-of-range label gives a NaN loss and no out-of-bounds
- * read; train.classif_finetune.train_classif checks its label list on the host, the ops wrappers do not).  One wave per row: m = max_j z_j; s = sum_j exp(z_j - m), lane i adding its columns i, i + 64, ... in ascending
- * order from +0, the 64 lane sums meeting in a butterfly (xor 32, 16, 8, 4, 2, 1); loss_rows[b] = log s + m - z_label (before any sum / mean).
- * A row's values do not depend on the rows around it. */
+ * utils/train_general.py:51-61.  logits: (B, C) fp32; labels: (B) int32 in [0, C).  One wave per row: m = max_j z_j by fmaxf (a NaN is
+ * skipped, a lane without a column holds -inf); s = sum_j exp(z_j - m), lane i adding its columns i, i + 64, ... in ascending order from +0,
+ * the 64 lane sums meeting in a butterfly (xor 32, 16, 8, 4, 2, 1); loss_rows[b] = (log s + m) - z_label, in this grouping (before any
+ * sum / mean).  Every operation rounds once, nothing is fused; expf and logf are the device library's (isx_debug_expf_logf reads them).
+ * A row's values do not depend on the rows around it, nor on B.
+ * Non-finite logits: a -inf column (a masked class) next to a finite one contributes exp = +0 exactly, its gradient is a zero with the sign
+ * of the scale, and the loss of a row whose label sits on it is +inf.  A row that holds +inf or a NaN, or nothing but -inf, is NaN
+ * throughout: its loss, every element of its gradient row, and the loss of its leaf (what F.cross_entropy gives).
+ * A label outside [0, C): no out-of-bounds read or write; the row's loss is NaN (and with it the loss of its leaf); isx_softmax_xent_bwd and
+ * isx_softmax_xent_leaves still write its gradient row, as (exp(z_j - m) / s) * scale -- no column carries the -1.
+ * train.classif_finetune.train_classif checks its label list on the host, the ops wrappers do not. */
 int isx_softmax_xent_fwd(const float* logits, const int32_t* labels, int64_t B, int C, float* loss_rows, isx_stream_t stream);
-/* dlogits[b][j] = (exp(z_j - m) / s - [j == label_b]) * scale * scale_dev[0]; scale_dev: autograd's grad_output left on the device (as
- * isx_triplet_loss_bwd_dev), or NULL for 1. */
+/* dlogits[b][j] = (exp(z_j - m) / s - [j == label_b]) * t with the ONE float t = scale * scale_dev[0] (t = scale where scale_dev is NULL);
+ * scale_dev: autograd's grad_output left on the device (as isx_triplet_loss_bwd_dev).  dlogits must not be logits. */
 int isx_softmax_xent_bwd(const float* logits, const int32_t* labels, int64_t B, int C, float scale, const float* scale_dev, float* dlogits,
                          isx_stream_t stream);
 /* The same loss and gradient for ALL micro-batches ("leaves") of an optimizer step in ONE launch.  logits: (leaves * k, C), labels: (leaves * k).
  * loss_leaf[l] = the leaf's row losses added in row order (before any averaging); dlogits rows as isx_softmax_xent_bwd forms them with
- * scale = scale_a * scale_b (1 / k when the loss is averaged, times the weight of the leaf in the mini-batch).  A leaf's loss and gradient are
- * the same bits whether it is launched alone or with its siblings -- the contract of isx_triplet_leaves. */
+ * scale = scale_a * scale_b, one float product (1 / k when the loss is averaged, times the weight of the leaf in the mini-batch): the bits of
+ * isx_softmax_xent_bwd at that product, and loss_leaf[l] the ordered sum of the rows isx_softmax_xent_fwd gives.  A leaf's loss and gradient
+ * are the same bits whether it is launched alone or with its siblings -- the contract of isx_triplet_leaves.  k <= 8192; dlogits must not be
+ * logits. */
 int isx_softmax_xent_leaves(const float* logits, const int32_t* labels, int leaves, int k, int C, float scale_a, float scale_b, float* loss_leaf,
                             float* dlogits, isx_stream_t stream);
 
@@ -584,6 +593,10 @@ void isx_debug_set_f16_tile(int t);
 /* Query rows of the LAST isx_cosine_topk_fast call on workspace `ws` (same arguments) that took the exact
  * fp32 fallback; -1 when that call ran the fp32 search as a whole.  Synchronises the device. */
 int isx_debug_fast_fallback_rows(const void* ws, int64_t M, int64_t N, int D, int k, int have_gallery_f16);
+/* e[i] = expf(x[i]), l[i] = logf(x[i]) for i < n, as the cross-entropy kernels of csrc/classif.hip evaluate them (the same translation unit and
+ * flags): the device's expf and logf are not correctly rounded, and the tests that pin those kernels bit for bit read them here.  Either output
+ * may be NULL; neither may overlap x.  A plain grid-stride kernel; sets nothing, changes no result. */
+int isx_debug_expf_logf(const float* x, int64_t n, float* e, float* l, isx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,9 @@ __device__ __forceinline__ float wave_fmax(float v) {
 
 // One wave on one row z[0 .. C): m = max_j z_j; s = sum_j exp(z_j - m), summed in this FIXED order: lane i adds its columns
 // i, i + 64, i + 128, ... in ascending order from +0, then the 64 lane sums meet in the butterfly of wave_sum (xor 32, 16, 8, 4, 2, 1).
-// Every lane returns the same (m, s).  s >= 1 (the maximum contributes exp(0)), so log s is finite whatever the spread of the logits.
+// Every lane returns the same (m, s).  On finite logits s >= 1 (the maximum contributes exp(0)), so log s is finite whatever their spread;
+// -inf columns add exp(-inf) = +0 exactly.  fmaxf skips a NaN, but the NaN column's own term is NaN; +inf gives inf - inf, a row of -inf only
+// gives -inf + inf: in all three s is NaN, and so are the row's loss and every element of its gradient.
 __device__ __forceinline__ void xent_row_stats(const float* __restrict__ z, int C, int lane, float& m, float& s) {
     float mx = -INFINITY;
     for (int j = lane; j < C; j += 64) mx = fmaxf(mx, z[j]);
@@ -26,14 +28,14 @@ __device__ __forceinline__ void xent_row_stats(const float* __restrict__ z, int 
     s = wave_sum(t);
 }
 
-// loss = log s + m - z_label.  A label outside [0, C) is the caller's error (train_classif checks its label list on the host); the kernel reads
+// loss = (log s + m) - z_label, in this grouping.  A label outside [0, C) is the caller's error (train_classif checks its label list on the host); the kernel reads
 // nothing out of bounds for it and reports NaN.
 __device__ __forceinline__ float xent_row_loss(const float* __restrict__ z, int C, int label, float m, float s) {
     if ((unsigned)label >= (unsigned)C) return __uint_as_float(0x7FC00000u);
     return logf(s) + m - z[label];
 }
 
-// dz_j = (exp(z_j - m) / s - [j == label]) * scale
+// dz_j = (exp(z_j - m) / s - [j == label]) * scale; a label outside [0, C) matches no column: the row is (exp(z_j - m) / s) * scale
 __device__ __forceinline__ void xent_row_grad(const float* __restrict__ z, int C, int label, int lane, float m, float s, float scale,
                                               float* __restrict__ dz) {
     for (int j = lane; j < C; j += 64) {
@@ -169,6 +171,15 @@ __global__ __launch_bounds__(256) void linear_wgrad_leaves_kernel(const float* _
         if (a < nn) *reinterpret_cast<float4*>(out + (int64_t)a * K) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
 }
 
+// Test hook: the expf and logf the kernels above call, one element per thread and trip -- this translation unit, these flags.
+__global__ __launch_bounds__(256) void debug_expf_logf_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ e, float* __restrict__ l) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float v = x[i];
+        if (e) e[i] = expf(v);
+        if (l) l[i] = logf(v);
+    }
+}
+
 }  // namespace isx
 
 using namespace isx;
@@ -241,5 +252,15 @@ ISX_API int isx_linear_wgrad_leaves(const float* dy, const float* x, int leaves,
     ISX_REQUIRE(gy <= 65535, "isx_linear_wgrad_leaves: N=%d too large", N);
     hipLaunchKernelGGL(linear_wgrad_leaves_kernel, dim3((unsigned)((K + 255) / 256), gy, (unsigned)leaves), dim3(256), 0, (hipStream_t)stream, dy, x, R, N, K, dw);
     ISX_CHECK_LAUNCH("isx_linear_wgrad_leaves");
+    return ISX_OK;
+}
+
+ISX_API int isx_debug_expf_logf(const float* x, int64_t n, float* e, float* l, isx_stream_t stream) {
+    ISX_REQUIRE(n >= 0, "isx_debug_expf_logf: bad shape n=%lld", (long long)n);
+    if (n == 0) return ISX_OK;
+    ISX_REQUIRE(x, "isx_debug_expf_logf: null pointer");
+    const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(debug_expf_logf_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, e, l);
+    ISX_CHECK_LAUNCH("isx_debug_expf_logf");
     return ISX_OK;
 }

@@ -102,6 +102,7 @@ _SIGNATURES = {
     "isx_debug_set_conv_cfg": (None, [I32]),
     "isx_debug_set_f16_tile": (None, [I32]),
     "isx_debug_fast_fallback_rows": (C.c_int, [VP, I64, I64, I32, I32, I32]),
+    "isx_debug_expf_logf": (C.c_int, [VP, I64, VP, VP, VP]),
 }
 EXPORTS = tuple(sorted(_SIGNATURES))
 

@@ -42,6 +42,17 @@ def test_new_entries_validate_their_arguments_without_gpu():
     assert lib.isx_softmax_xent_leaves(None, None, -1, 8, 464, 1.0, 1.0, None, None, None) == -1 and b"bad shape" in err()
     assert lib.isx_softmax_xent_leaves(None, None, 2, 8, 464, 1.0, 1.0, None, None, None) == -1 and b"null pointer" in err()
     assert lib.isx_softmax_xent_leaves(None, None, 0, 8, 464, 1.0, 1.0, None, None, None) == 0           # leaves == 0: a no-op
+    # dlogits == logits is refused (the kernels take both as __restrict__; the leaves kernel reads z_label while other lanes write their dz)
+    import ctypes
+    buf = (ctypes.c_float * 64)()
+    ptr, other = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_void_p(ctypes.addressof(buf) + 128)
+    assert lib.isx_softmax_xent_bwd(ptr, other, 1, 4, 1.0, None, ptr, None) == -1 and b"aliases" in err()
+    assert lib.isx_softmax_xent_leaves(ptr, other, 1, 1, 4, 1.0, 1.0, other, ptr, None) == -1 and b"aliases" in err()
+    # the test hook for the device's expf / logf
+    assert "isx_debug_expf_logf" in _lib.EXPORTS
+    assert lib.isx_debug_expf_logf(ptr, -1, ptr, ptr, None) == -1 and b"bad shape" in err()
+    assert lib.isx_debug_expf_logf(None, 4, ptr, ptr, None) == -1 and b"null pointer" in err()
+    assert lib.isx_debug_expf_logf(None, 0, None, None, None) == 0
     assert lib.isx_gap_bwd_nhwc(None, 2, 7, 0, 2048, None, None) == -1 and b"bad shape" in err()
     assert lib.isx_gap_bwd_nhwc(None, 2, 7, 7, 2046, None, None) == -1 and b"multiple of 4" in err()
     assert lib.isx_gap_bwd_nhwc(None, 2, 7, 7, 2048, None, None) == -1 and b"null" in err()
