@@ -96,28 +96,31 @@ int isx_bias_act_inplace(float* y, const float* bias, const float* residual, int
 /* Image ingest (next-scope row f4): transforms.ToTensor() + transforms.Normalize(m, s) of the test mains
  * (test/classif_finetune_test.py:62-73, classif_regions_test.py:55-65, siamese_*_test.py) from decoded RGB bytes:
  * out[b][c][h][w] = (img[b][h][w][c] / 255 - mean[c]) / std[c], fp32, same operation order as torch.
- * img: (B,H,W,3) uint8 RGB; out: (B,3,H,W) fp32 in NCHW memory, or channels-last memory ((B,H,W,3)) when channels_last != 0. */
+ * img: (B,H,W,3) uint8 RGB, any alignment; out: (B,3,H,W) fp32 in NCHW memory, or channels-last memory ((B,H,W,3)) when channels_last != 0,
+ * 16-B aligned (refused otherwise: four pixels go out as 16-byte stores). */
 int isx_images_u8_to_f32(const uint8_t* img, int64_t B, int H, int W, float mean0, float mean1, float mean2, float std0, float std1,
                          float std2, int channels_last, float* out, isx_stream_t stream);
 
 /* Stem of the same trunk: relu(conv7x7 + bias) -> MaxPool2d(3, stride 2, padding 1) (torchvision ResNet stem as split
  * by model/nn_utils.py:56-71), epilogue and pooling in ONE pass over the channels-last convolution output:
  * out[b][ho][wo][c] = relu(max_{3x3 window, in bounds} y[b][2ho-1+kh][2wo-1+kw][c] + bias[c]).
- * y: (B,H,W,C), out: (B,Ho,Wo,C), Ho = (H-1)/2 + 1; C % 4 == 0. */
+ * y: (B,H,W,C), out: (B,Ho,Wo,C), Ho = (H-1)/2 + 1; C % 4 == 0; y, bias and out 16-B aligned (refused otherwise). */
 int isx_bias_relu_maxpool_nhwc(const float* y, const float* bias, int64_t B, int H, int W, int C, float* out, isx_stream_t stream);
 
 /* conv2 + conv3 of a torchvision Bottleneck with 64 mid channels (the first ResNet stage; BN folded; model/nn_utils.py:56-71) as ONE kernel:
  *   y = act( W3 . relu(conv3x3(x, W2) + b2) + b3 + (residual ? residual : 0) ),
  * the 64-channel mid activation stays on chip (registers -> LDS -> second MFMA loop).  Same fma chains as isx_conv3x3_nhwc followed by
  * isx_conv1x1_nhwc (bit-identical results).  x: (B,H,W,Cin), Cin % 32 == 0; w2_ohwi: (64,3,3,Cin); b2: (64); w3t: (64,256) = the 1x1
- * weight (256,64) TRANSPOSED; b3: (256); y / residual: (B,Ho,Wo,256); Cout must be 256. */
+ * weight (256,64) TRANSPOSED; b3: (256); y / residual: (B,Ho,Wo,256); Cout must be 256.  x, w2_ohwi and w3t 16-B aligned (refused otherwise);
+ * b2, b3, residual and y: any fp32 alignment.  y must not alias x or residual. */
 int isx_conv3x3_expand_nhwc(const float* x, int64_t B, int H, int W, int Cin, const float* w2_ohwi, const float* b2, int stride,
                             const float* w3t, int Cout, const float* b3, const float* residual, int relu, float* y, isx_stream_t stream);
 
 /* The same for the FIRST block of that stage, whose shortcut is a 1x1 projection of the 64-channel block input x2 (stride 1):
  *   y = act( [W3 | Wd] . [relu(conv3x3(t, W2) + b2) ; x2] + bias )  -- one fma chain per output over the 64 mid channels, then the 64 channels
  * of x2, as isx_conv3x3_nhwc followed by isx_conv1x1_dual_nhwc.  t: (B,H,W,Cin); x2: (B,H,W,64); wcat_t: (128,256) = [W3 | Wd] TRANSPOSED;
- * bias: (256) = b3 + bd; y: (B,H,W,256). */
+ * bias: (256) = b3 + bd; y: (B,H,W,256).  t, x2, w2_ohwi and wcat_t 16-B aligned (refused otherwise); b2, bias and y: any fp32 alignment.
+ * y must not alias t or x2. */
 int isx_conv3x3_expand_dual_nhwc(const float* t, int64_t B, int H, int W, int Cin, const float* w2_ohwi, const float* b2, const float* x2,
                                  const float* wcat_t, int Cout, const float* bias, int relu, float* y, isx_stream_t stream);
 
@@ -156,7 +159,8 @@ int isx_conv1x1_nhwc(const float* x, int64_t M, int Cin, const float* w, int Cou
  * conv3 + downsample, same call sites) as ONE GEMM over the output pixels:
  *   y[m][co] = act( sum_c t[m][c] w_cat[co][c]  +  sum_c x[pix(m)][c] w_cat[co][K1 + c]  +  bias[co] ),
  * pix(m) = the input pixel (ho*stride, wo*stride) of output pixel m; one fp32 fma chain per output (t's channels first).
- * t: (B,Ho,Wo,K1); x: (B,H,W,K2); w_cat: (Cout, K1 + K2); y: (B,Ho,Wo,Cout); K1 % 32 == K2 % 32 == 0. */
+ * t: (B,Ho,Wo,K1); x: (B,H,W,K2); w_cat: (Cout, K1 + K2); y: (B,Ho,Wo,Cout); K1 % 32 == K2 % 32 == 0.  t, x and w_cat 16-B aligned (refused
+ * otherwise); bias and y: any fp32 alignment.  y must not alias t or x. */
 int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_t B, int H, int W, int K2, int stride, const float* w_cat,
                           int Cout, const float* bias, int relu, float* y, isx_stream_t stream);
 
@@ -164,7 +168,8 @@ int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_t B, int
  * matrix cores: M = B*Ho*Wo output pixels, K = 9*Cin in (kh, kw, ci) order (one fp32 fma chain per output, bit-exact
  * vs the oracle), epilogue act(. + bias[co] + residual) fused.  Replaces conv2 of the torchvision Bottleneck and the
  * convolutions of BasicBlock (same call sites as isx_conv1x1_nhwc).  x: (B,H,W,Cin); w_ohwi: (Cout,3,3,Cin);
- * y / residual: (B,Ho,Wo,Cout), Ho = (H-1)/stride + 1.  Cin % 32 == 0. */
+ * y / residual: (B,Ho,Wo,Cout), Ho = (H-1)/stride + 1.  Cin % 32 == 0.  x and w_ohwi 16-B aligned (refused otherwise); bias, residual and y:
+ * any fp32 alignment.  y must not alias x or residual. */
 int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, const float* w_ohwi, int Cout, int stride,
                      const float* bias, const float* residual, int relu, float* y, isx_stream_t stream);
 

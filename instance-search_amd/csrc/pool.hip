@@ -614,6 +614,7 @@ ISX_API int isx_images_u8_to_f32(const uint8_t* img, int64_t B, int H, int W, fl
     ISX_REQUIRE(std0 != 0.0f && std1 != 0.0f && std2 != 0.0f, "isx_images_u8_to_f32: zero std");
     if (B == 0) return ISX_OK;
     ISX_REQUIRE(img && out, "isx_images_u8_to_f32: null pointer");
+    ISX_REQUIRE((((uintptr_t)out) % 16) == 0, "isx_images_u8_to_f32: out must be 16-B aligned");       // (the float4 stores of both layouts)
     const int64_t quads = (B * H * W + 3) / 4, blocks = (quads + 255) / 256;
     hipLaunchKernelGGL(isx::images_u8_to_f32_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, img, B,
                        H * W, mean0, mean1, mean2, std0, std1, std2, channels_last ? 1 : 0, out);

@@ -1,0 +1,172 @@
+"""Guarded device buffers for the tests that call the C ABI directly (test_gpu_trunk_guards.py, test_gpu_retrieval_guards.py).
+
+A Region is ONE allocation: a leading guard, the body, a trailing guard.  The guards hold a sentinel bit pattern and are compared bit for bit
+after every launch; an OUTPUT body starts as a poison pattern (a NaN with a payload no kernel produces, or an integer no kernel produces) and
+must not hold it afterwards; an INPUT body holds the data and its guards are NaNs, so that an operand read past either end reaches the output
+as a NaN.  Unlike _guarded / _guards_intact of test_gpu_triplet_chains.py the guard size is chosen per call (it has to cover every address a
+dead row of the last tile maps to) and the body may start `offset` elements past a 256-byte boundary (offset = 1: a pointer that is only
+4-byte aligned).  All comparisons are on integer views: a legitimate NaN is never mistaken for the poison."""
+import numpy as np
+import torch
+
+POISON_F32 = 0x7FC0DEAD                      # a quiet NaN with a payload
+GUARD_OUT_F32 = 0xC640E400                   # -12345.0f
+GUARD_IN_F32 = 0x7FC0BEEF                    # NaN around the operands
+POISON_I64 = -(1 << 62)
+POISON_I32 = -(1 << 30)
+GUARD_I64 = -12345
+POISON_F64 = 0x7FF8DEAD0000DEAD              # a quiet NaN with a payload, as int64 bits
+GUARD_U8 = 0xA5
+POISON_U8 = 0xCD
+
+_KIND = {  # kind -> (storage dtype, view dtype, guard, poison)
+    "f32": (torch.int32, torch.float32, GUARD_OUT_F32, POISON_F32),
+    "i32": (torch.int32, torch.int32, GUARD_I64, POISON_I32),
+    "i64": (torch.int64, torch.int64, GUARD_I64, POISON_I64),
+    "f64": (torch.int64, torch.float64, GUARD_I64, POISON_F64),
+    "u8": (torch.uint8, torch.uint8, GUARD_U8, POISON_U8),
+}
+
+
+def _signed(v, dtype):
+    bits = {torch.int32: 32, torch.int64: 64}.get(dtype)
+    return v - (1 << bits) if bits and v >= 1 << (bits - 1) else v
+
+
+class Region:
+    def __init__(self, kind, shape, guard, offset=0, data=None, guard_value=None):
+        store, view, g, poison = _KIND[kind]
+        self.kind, self.shape, self.view_dtype = kind, tuple(int(s) for s in np.atleast_1d(shape)), view
+        self.n = int(np.prod(self.shape))
+        item = torch.empty((), dtype=store).element_size()
+        per256 = 256 // item
+        lead = -(-int(guard) // per256) * per256              # the body at offset 0 sits on a 256-byte boundary of the allocation
+        self.start = lead + int(offset)
+        self.guard_value = _signed(g if guard_value is None else guard_value, store)
+        self.poison = _signed(poison, store)
+        self.buf = torch.full((self.start + self.n + int(guard),), self.guard_value, dtype=store, device="cuda")
+        assert self.buf.data_ptr() % 256 == 0
+        body = self.buf[self.start:self.start + self.n]
+        if data is None:
+            body.fill_(self.poison)
+        else:
+            a = np.ascontiguousarray(data)
+            assert a.size == self.n and a.dtype.itemsize == item, (a.shape, a.dtype, self.shape)
+            body.copy_(torch.from_numpy(a.reshape(-1).view({1: np.uint8, 4: np.int32, 8: np.int64}[item])))
+        self.ptr = self.buf.data_ptr() + self.start * item
+        assert self.ptr % item == 0 and (offset or self.ptr % 256 == 0)
+
+    @property
+    def body(self):
+        """The body as a tensor of the element type (a view: no copy)."""
+        b = self.buf[self.start:self.start + self.n]
+        return (b if b.dtype == self.view_dtype else b.view(self.view_dtype)).view(*self.shape)
+
+    def raw(self):
+        """The body as the integer storage type, flat: what bit comparisons use."""
+        return self.buf[self.start:self.start + self.n]
+
+    def guards_intact(self):
+        return bool((self.buf[:self.start] == self.guard_value).all()) and bool((self.buf[self.start + self.n:] == self.guard_value).all())
+
+    def unwritten(self):
+        return int((self.raw() == self.poison).sum())
+
+    def host(self):
+        return self.body.cpu().numpy()
+
+
+def out_f32(shape, guard, offset=0):
+    return Region("f32", shape, guard, offset)
+
+
+def out_i64(shape, guard, offset=0):
+    return Region("i64", shape, guard, offset)
+
+
+def out_f64(shape, guard, offset=0):
+    return Region("f64", shape, guard, offset)
+
+
+def in_f32(a, guard=1024, offset=0):
+    """An fp32 operand between NaN guards."""
+    a = np.ascontiguousarray(a, np.float32)
+    return Region("f32", a.shape, guard, offset, data=a, guard_value=GUARD_IN_F32)
+
+
+def in_i32(a, guard=1024, offset=0):
+    """int32 labels between guards of a label no case uses."""
+    a = np.ascontiguousarray(a, np.int32)
+    return Region("i32", a.shape, guard, offset, data=a)
+
+
+def in_i64(a, guard=1024, offset=0):
+    a = np.ascontiguousarray(a, np.int64)
+    return Region("i64", a.shape, guard, offset, data=a)
+
+
+def in_f32_io(a, guard, offset=0):
+    """An fp32 buffer a kernel updates in place: the data between SENTINEL guards."""
+    a = np.ascontiguousarray(a, np.float32)
+    return Region("f32", a.shape, guard, offset, data=a)
+
+
+def workspace(nbytes, guard=4096):
+    """A byte workspace of exactly nbytes on a 256-byte boundary, at least 4 KiB of a byte pattern on both sides."""
+    assert guard >= 4096
+    return Region("u8", (max(int(nbytes), 1),), guard)
+
+
+def ptr(r):
+    return None if r is None else r.ptr
+
+
+def assert_clean(outs, ins=(), what=""):
+    """After a launch: every guard intact, no output element still poison.  Synchronises (the reductions read the buffers)."""
+    for i, r in enumerate(ins):
+        assert r is None or r.guards_intact(), ("guard of input %d overwritten" % i, what)
+    for i, r in enumerate(outs):
+        assert r.guards_intact(), ("store outside output %d" % i, what)
+        left = r.unwritten()
+        assert left == 0, ("output %d: %d of %d elements never written" % (i, left, r.n), what)
+
+
+def bits(a):
+    """Host array -> its unsigned bit pattern (fp32 -> uint32, fp64 -> uint64)."""
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def assert_bits(got, want, what=""):
+    got = got.host() if isinstance(got, Region) else (got.cpu().numpy() if isinstance(got, torch.Tensor) else got)
+    want = np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    bad = bits(got) != bits(want)
+    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist(), got[bad][:4].tolist(), want[bad][:4].tolist())
+
+
+# ---- host arithmetic of the launchers (csrc/gemm.hip, csrc/conv.hip), restated so that a case can assert the path it means to take ----------
+def tail_split_rows(M, N, slots=512):
+    """gemm_tail_split_rows: rows covered by whole rounds of 128x128 tiles when the last round is partial (0: no split)."""
+    tn = (N + 127) // 128
+    tiles = ((M + 127) // 128) * tn
+    if tn > slots or slots % tn:
+        return 0
+    rounds = tiles // slots
+    rem = tiles - rounds * slots
+    if rounds < 1 or rem == 0 or rem > slots * 4 // 5:
+        return 0
+    return rounds * (slots // tn) * 128
+
+
+def pos_major_rows(B, H, W, Cin, Ho, Wo, Cout, tiles_n64):
+    """conv3x3_pos_major_rows: virtual rows of a position-major launch, 0 = pixel-major."""
+    P = Ho * Wo
+    ok = Cin % 64 == 0 and B >= 128 and P <= 28 * 28 and (128 * H * W + 2 * W + 4) * Cin * 4 < (1 << 32) and 128 * P * Cout * 4 < (1 << 31)
+    groups = (B + 127) // 128
+    return groups * P * 128 if ok and groups * P * 2 * tiles_n64 < (1 << 31) else 0
+
+
+def stream_applicable(M, Cin, Cout, x_ptr):
+    """conv1x1_stream_applicable"""
+    return Cin == 64 and Cout in (64, 256) and M >= 16384 and x_ptr % 16 == 0

@@ -76,6 +76,22 @@ def test_argument_validation_without_gpu():
     assert lib.isx_triplet_leaves(None, 2, 0, 64, 0.1, 1, 1.0, 1.0, None, None, None) == -1 and b"bad shape" in lib.isx_last_error()
     assert lib.isx_triplet_leaves(None, 2, 8, 64, 0.1, 1, 1.0, 1.0, None, None, None) == -1 and b"null pointer" in lib.isx_last_error()
     assert lib.isx_triplet_leaves(None, 0, 8, 64, 0.1, 1, 1.0, 1.0, None, None, None) == 0
+    # operands that the trunk kernels fetch with 16-byte loads: a non-null pointer off a 16-byte boundary is refused before any launch
+    # (24 = 16 + 8; the other pointers are non-null, distinct and aligned; none is dereferenced on the host)
+    def refused(entry, args, aligned_args):
+        for i in aligned_args:
+            a = list(args)
+            a[i] = 24
+            assert getattr(lib, entry)(*a) == -1 and b"16-B aligned" in lib.isx_last_error() and entry.encode() in lib.isx_last_error(), (entry, i)
+    P = [256 * (i + 1) for i in range(8)]
+    refused("isx_conv3x3_nhwc", [P[0], 1, 1, 1, 32, P[1], 32, 1, P[2], None, 1, P[3], None], (0, 5))
+    refused("isx_conv1x1_dual_nhwc", [P[0], 32, P[1], 1, 1, 1, 32, 1, P[2], 32, P[3], 1, P[4], None], (0, 2, 8))
+    refused("isx_conv3x3_expand_nhwc", [P[0], 1, 1, 1, 32, P[1], P[2], 1, P[3], 256, P[4], None, 1, P[5], None], (0, 5, 8))
+    refused("isx_conv3x3_expand_dual_nhwc", [P[0], 1, 1, 1, 32, P[1], P[2], P[3], P[4], 256, P[5], 1, P[6], None], (0, 5, 7, 8))
+    refused("isx_conv3x3_expand128_nhwc", [P[0], 1, 1, 1, 64, P[1], P[2], P[3], 128, P[4], None, 1, P[5], None], (0, 5, 7))
+    refused("isx_stem7x7_pool_nhwc", [P[0], 1, 8, 8, P[1], P[2], P[3], None], (0,))
+    refused("isx_images_u8_to_f32", [P[0], 1, 2, 2, 0.5, 0.5, 0.5, 0.25, 0.25, 0.25, 1, P[1], None], (11,))
+    assert lib.isx_bias_relu_maxpool_nhwc(P[0], P[1], 1, 2, 2, 4, 24, None) == -1 and b"16-B alignment required" in lib.isx_last_error()
     # empty problems are no-ops
     assert lib.isx_l2norm_rows(None, 0, 16, 1e-10, None, None) == 0
     assert lib.isx_cosine_sim(None, 0, None, 0, 8, None, None) == 0
