@@ -220,6 +220,42 @@ int isx_region_topk_nhwc(const float* cls, int64_t B, int K, int Hp, int Wp, int
 int isx_region_gather_l2_nhwc(const float* fmap, int64_t B, int C, int Hf, int Wf, int kh, int kw, const int64_t* flat_idx, int k,
                               int Wp, const float* shift_hwc, float eps, float* rows, isx_stream_t stream);
 
+/* The TRAINING form of the region descriptor's first step (model/siamese.py:191-219 under autograd, train/siamese_regions.py): the reference
+ * sends each of an image's k windows through NormalizeL2 -> Shift -> Linear and sums the k results; the Linear is linear, so
+ * sum_w (W x1_w + b) = W (sum_w x1_w) + k b, and the 822 MB Linear runs on ONE row per image.  These two entries are the step in front of it and
+ * its backward pass.  fmap, dfmap, add: (B,Hf,Wf,C) channels-last; rows, g: (B,F), F = C*kh*kw in the Linear's stored (c, a, b) column order
+ * (no permuted copy of the weight, the Shift or the momentum); flat_idx: (B,k) as isx_region_topk_nhwc writes it, (row, col) = (fi / Wp,
+ * fi % Wp), Wp = Wf - kw + 1; n2, cw: (B,k).  An entry fi outside [0, (Hf-kh+1) * Wp) is SKIPPED: it contributes nothing, reads nothing,
+ * and its n2 / cw are +0.  C % 4 == 0, B < 65536, 1 <= k <= 1024.  16-byte alignment is required (and checked) of the operands the kernels
+ * reach with vector accesses or in aligned runs: fmap, rows, shift; fmap, g, add, dfmap.  n2 and cw are plain float arrays.
+ *
+ * isx_region_sum_l2_nhwc: with v_w[j] = fmap[b][row_w + a][col_w + bb][c], j = (c kh + a) kw + bb:
+ *   n2_w = ss_w + eps, ss_w = sum_j v_w[j]^2;  t_w[j] = v_w[j] / sqrtf(n2_w) + (shift ? shift[j] : +0): one IEEE division and one add, as
+ *   isx_region_gather_l2 forms it;  rows[b][j] = ((t_0[j] + t_1[j]) + ...) + t_{k-1}[j] over the windows that are not skipped, in ascending
+ *   window order, STARTING FROM the first of them (no +0 in front); an image with no window at all gets +0.  n2 is written for the backward.
+ * The order of ss_w (and of c_w below) is ONE order for every shape, a function of the window alone -- that of isx_region_gather_l2_nhwc:
+ *   the window is walked as its (a, bb, c) row (kh runs of kw*C contiguous floats of the map) in float4 groups; thread t of 1024 owns the
+ *   groups t, t + 1024, ... and adds the four products of a group to its accumulator ONE BY ONE (x, y, z, w), from +0; the 64 lanes of a wave
+ *   meet in the xor butterfly 32, 16, 8, 4, 2, 1; the 16 wave sums are added in wave order from +0.
+ *
+ * isx_region_sum_l2_bwd_nhwc: g = the gradient wrt rows (shared by the k windows of an image).
+ *   c_w = sum_j v_w[j] g[j] in the order above (written to the caller's workspace cw; the entry allocates nothing);
+ *   dv_w[j] = (n2_w g[j] - v_w[j] c_w) * inv_w, inv_w = 1 / (n2_w sqrtf(n2_w)): formula and grouping of isx_l2norm_rows_bwd, every operation
+ *   rounded, nothing fused;  dfmap[b][y][x][c] = the sum of dv_w[(c, y - row_w, x - col_w)] over the windows that cover (y, x) and are not
+ *   skipped, added in ascending w, fp32, from +0 (a pixel no window covers: +0); then the further gradient of the map, as one fp32 add, LAST.
+ *   add (NULL: none) holds ONE map per add_every images, (B / add_every, Hf, Wf, C): image b with b % add_every == 0 adds
+ *   add[b / add_every][y][x][c], the other images add nothing (add_every = 1: every image its own map; the region head passes 3: only the
+ *   anchor of a triplet carries the class term).  B % add_every == 0.  An image without a map gets the bits a map of +0 would give it.
+ *   Gather form: every destination sums its own list in a fixed order, no atomics; an image's output depends on no other image.
+ *   dfmap must not overlap fmap, g or add (the entry refuses equal base pointers; partial overlap is the caller's to avoid).
+ * Both stage a slice of up to 64 channels in LDS (the whole Hf x Wf map resp. the kh x kw window of g): Hf*Wf*5 + 2 k resp. kh*kw*4 + 5 k floats
+ * must fit 64 KB; the slice width only groups outputs -- same bits. */
+int isx_region_sum_l2_nhwc(const float* fmap, int64_t B, int C, int Hf, int Wf, int kh, int kw, const int64_t* flat_idx, int k, int Wp,
+                           const float* shift, float eps, float* rows, float* n2, isx_stream_t stream);
+int isx_region_sum_l2_bwd_nhwc(const float* fmap, const float* g, const float* n2, int64_t B, int C, int Hf, int Wf, int kh, int kw,
+                               const int64_t* flat_idx, int k, int Wp, const float* add, int add_every, float* cw, float* dfmap,
+                               isx_stream_t stream);
+
 /* ---- retrieval ------------------------------------------------------------- */
 
 /* test/classif_finetune_test.py:82 (and classif_regions_test.py:73,

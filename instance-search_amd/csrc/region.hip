@@ -199,6 +199,8 @@ __global__ __launch_bounds__(1024) void region_gather_l2_nhwc_kernel(const float
 
 }  // namespace isx
 
+#include "region_sum_kernel.hpp"
+
 using namespace isx;
 
 ISX_API int isx_best_location_desc(const float* cls, int64_t B, int K, int Hp, int Wp, float eps, float* desc,
@@ -275,5 +277,55 @@ ISX_API int isx_region_gather_l2_nhwc(const float* fmap, int64_t B, int C, int H
     hipLaunchKernelGGL(region_gather_l2_nhwc_kernel, dim3((unsigned)k, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, fmap, C, Hf, Wf, kh, kw,
                        flat_idx, Wp, shift_hwc, eps, rows);
     ISX_CHECK_LAUNCH("isx_region_gather_l2_nhwc");
+    return ISX_OK;
+}
+
+// ---- training form: the k windows of an image gathered, L2-normalised, shifted and summed into ONE row, and its backward pass ----------------
+static int region_sum_shape_ok(int64_t B, int C, int Hf, int Wf, int kh, int kw, int k, int Wp) {
+    return B >= 0 && B < 65536 && C > 0 && Hf > 0 && Wf > 0 && kh > 0 && kw > 0 && kh <= Hf && kw <= Wf && k > 0 && k <= 1024 && Wp == Wf - kw + 1 &&
+           (int64_t)C * kh * kw < (1ll << 31) && (int64_t)Hf * Wf * C < (1ll << 31);
+}
+
+ISX_API int isx_region_sum_l2_nhwc(const float* fmap, int64_t B, int C, int Hf, int Wf, int kh, int kw, const int64_t* flat_idx, int k, int Wp,
+                                   const float* shift, float eps, float* rows, float* n2, isx_stream_t stream) {
+    ISX_REQUIRE(region_sum_shape_ok(B, C, Hf, Wf, kh, kw, k, Wp), "isx_region_sum_l2_nhwc: bad shape B=%lld C=%d Hf=%d Wf=%d k=%dx%d n=%d Wp=%d",
+                (long long)B, C, Hf, Wf, kh, kw, k, Wp);
+    ISX_REQUIRE(C % 4 == 0 && (((uintptr_t)fmap | (uintptr_t)rows | (uintptr_t)shift) % 16) == 0,
+                "isx_region_sum_l2_nhwc: C=%d must be a multiple of 4 and the pointers 16-B aligned", C);
+    const int64_t HW = (int64_t)Hf * Wf;
+    const int CS = region_slice(HW, HW + 2 * (int64_t)k);
+    ISX_REQUIRE(CS > 0, "isx_region_sum_l2_nhwc: a %dx%d map does not fit the LDS staging", Hf, Wf);
+    if (B == 0) return ISX_OK;
+    ISX_REQUIRE(fmap && flat_idx && rows && n2, "isx_region_sum_l2_nhwc: null pointer");
+    hipLaunchKernelGGL(region_window_stat_kernel<false>, dim3((unsigned)k, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, fmap,
+                       (const float*)nullptr, C, Hf, Wf, kh, kw, flat_idx, Wp, eps, n2);
+    ISX_CHECK_LAUNCH("isx_region_sum_l2_nhwc");
+    hipLaunchKernelGGL(region_sum_l2_nhwc_kernel, dim3((unsigned)((C + CS - 1) / CS), (unsigned)B), dim3(256),
+                       (size_t)(HW * (CS + 1) + 2 * k) * 4, (hipStream_t)stream, fmap, C, Hf, Wf, kh, kw, flat_idx, k, Wp, shift, (const float*)n2, CS,
+                       rows);
+    ISX_CHECK_LAUNCH("isx_region_sum_l2_nhwc");
+    return ISX_OK;
+}
+
+ISX_API int isx_region_sum_l2_bwd_nhwc(const float* fmap, const float* g, const float* n2, int64_t B, int C, int Hf, int Wf, int kh, int kw,
+                                       const int64_t* flat_idx, int k, int Wp, const float* add, int add_every, float* cw, float* dfmap,
+                                       isx_stream_t stream) {
+    ISX_REQUIRE(region_sum_shape_ok(B, C, Hf, Wf, kh, kw, k, Wp) && add_every >= 1 && B % add_every == 0,
+                "isx_region_sum_l2_bwd_nhwc: bad shape B=%lld C=%d Hf=%d Wf=%d k=%dx%d n=%d Wp=%d add_every=%d", (long long)B, C, Hf, Wf, kh, kw, k, Wp,
+                add_every);
+    ISX_REQUIRE(C % 4 == 0 && (((uintptr_t)fmap | (uintptr_t)g | (uintptr_t)add | (uintptr_t)dfmap) % 16) == 0,
+                "isx_region_sum_l2_bwd_nhwc: C=%d must be a multiple of 4 and the pointers 16-B aligned", C);
+    const int CS = region_slice((int64_t)kh * kw, 5 * (int64_t)k);
+    ISX_REQUIRE(CS > 0, "isx_region_sum_l2_bwd_nhwc: a %dx%d window does not fit the LDS staging", kh, kw);
+    if (B == 0) return ISX_OK;
+    ISX_REQUIRE(fmap && g && n2 && flat_idx && cw && dfmap && dfmap != fmap && dfmap != add && dfmap != g,
+                "isx_region_sum_l2_bwd_nhwc: null or aliased pointer");
+    hipLaunchKernelGGL(region_window_stat_kernel<true>, dim3((unsigned)k, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, fmap, g, C, Hf, Wf, kh, kw,
+                       flat_idx, Wp, 0.0f, cw);
+    ISX_CHECK_LAUNCH("isx_region_sum_l2_bwd_nhwc");
+    hipLaunchKernelGGL(region_sum_l2_bwd_nhwc_kernel, dim3((unsigned)((C + CS - 1) / CS), (unsigned)B), dim3(256),
+                       (size_t)((int64_t)CS * kh * kw + 5 * k) * 4, (hipStream_t)stream, fmap, g, n2, (const float*)cw, C, Hf, Wf, kh, kw, flat_idx, k, Wp,
+                       add, add_every, CS, dfmap);
+    ISX_CHECK_LAUNCH("isx_region_sum_l2_bwd_nhwc");
     return ISX_OK;
 }

@@ -101,25 +101,39 @@ class ClassifHeadEngine(object):
         R = (M // leaves) * loc
         if R > MAX_ROWS_PER_LEAF:
             raise _lib.IsxError("classifier engine: %d window rows per micro-batch (at most %d)" % (R, MAX_ROWS_PER_LEAF))
-        pooled = ops.boxpool_s1_nhwc(y_all, kh, kw) if ops.boxpool_s1_applicable_nhwc(y_all) else ops.boxpool_s1(y_all.float(), kh, kw)
-        rows = pooled.permute(0, 2, 3, 1).reshape(M * loc, K)                  # a view of the channels-last result: image-major, then window
-        if not rows.is_contiguous():
-            rows = rows.contiguous()
-        wp, bp = self._padded()
-        Np = wp.size(0)
-        logits = ops.head_linear(rows, wp, bp)
-        if Np != N:
-            logits = logits[:, :N].contiguous()
+        rows, logits, wp = self.scores(y_all)
         per_leaf, dz = ops.softmax_xent_leaves(logits, labels if loc == 1 else labels.repeat_interleave(loc), leaves, scale_a, scale_b)
-        if cls.weight.requires_grad:
-            lo, hi = slices[cls.weight]
-            flat_all[:, lo:hi] += ops.linear_wgrad_leaves(dz, rows, leaves).view(leaves, -1)
-        if cls.bias is not None and cls.bias.requires_grad:
-            lo, hi = slices[cls.bias]
-            flat_all[:, lo:hi] += ops.colsum_leaves(dz, leaves)
+        self.add_grads(dz, rows, leaves, flat_all, slices)
         if not need_dy:
             return per_leaf, None
         dpool = ops.head_linear_dgrad(dz, wp)                   # (M loc, K); against the class-padded weight
         if loc == 1:                                            # the window spans the map: one term per pixel, the division alone
             return per_leaf, ops.gap_bwd_nhwc(dpool, H, W)
         return per_leaf, ops.boxpool_s1_bwd_nhwc(dpool.view(M, Ho, Wo, K).permute(0, 3, 1, 2), H, W, kh, kw)
+
+    def scores(self, y_all):
+        """pool -> classifier on every window of every image: (pooled window rows (M loc, K), image-major, then window; class scores (M loc, N);
+        the class-padded weight the scores were formed against -- what head_linear_dgrad takes)."""
+        M, K = y_all.shape[:2]
+        kh, kw = self.window()
+        N = self.cls.weight.size(0)
+        pooled = ops.boxpool_s1_nhwc(y_all, kh, kw) if ops.boxpool_s1_applicable_nhwc(y_all) else ops.boxpool_s1(y_all.float(), kh, kw)
+        rows = pooled.permute(0, 2, 3, 1).reshape(-1, K)                       # a view of the channels-last result: image-major, then window
+        if not rows.is_contiguous():
+            rows = rows.contiguous()
+        wp, bp = self._padded()
+        logits = ops.head_linear(rows, wp, bp)
+        if wp.size(0) != N:
+            logits = logits[:, :N].contiguous()
+        return rows, logits, wp
+
+    def add_grads(self, dz, rows, leaves, flat_all, slices):
+        """ADDS the classifier's per-leaf gradients (dz: gradient wrt the scores of `rows`, equal row counts per leaf) into the leaves' rows of
+        flat_all at the parameters' slices."""
+        cls = self.cls
+        if cls.weight.requires_grad:
+            lo, hi = slices[cls.weight]
+            flat_all[:, lo:hi] += ops.linear_wgrad_leaves(dz, rows, leaves).view(leaves, -1)
+        if cls.bias is not None and cls.bias.requires_grad:
+            lo, hi = slices[cls.bias]
+            flat_all[:, lo:hi] += ops.colsum_leaves(dz, leaves)

@@ -498,6 +498,63 @@ def region_gather_l2_nhwc(fmap, kh, kw, flat_idx, Wp, shift_hwc=None, eps=EPS):
     return rows
 
 
+def _region_sum_args(fmap, flat_idx, kh, kw, what):
+    if not (isinstance(fmap, torch.Tensor) and fmap.is_cuda and fmap.dtype == torch.float32 and fmap.dim() == 4 and _is_nhwc(fmap)
+            and fmap.shape[1] % 4 == 0):
+        raise _lib.IsxError("%s: fmap must be a channels-last float32 CUDA tensor (B,C,Hf,Wf) with C %% 4 == 0 (libisx has no CPU path)" % what)
+    _on_current_device(fmap, "fmap")
+    flat_idx = _typed(flat_idx, torch.int64, "flat_idx")
+    if flat_idx.dim() != 2 or flat_idx.size(0) != fmap.size(0) or flat_idx.size(1) < 1:
+        raise _lib.IsxError("%s: flat_idx %s is not (B = %d, k >= 1)" % (what, tuple(flat_idx.shape), fmap.size(0)))
+    return flat_idx, fmap.size(1) * kh * kw
+
+
+def region_sum_l2_nhwc(fmap, kh, kw, flat_idx, Wp, shift=None, eps=EPS):
+    """The k windows of every image gathered, L2-normalised, shifted and summed in window order (isx_region_sum_l2_nhwc): fmap channels-last
+    (B,C,Hf,Wf), flat_idx (B,k) -> (rows (B, C*kh*kw) in (c, a, b) order -- the Linear's stored column order, `shift` in that order too --,
+    n2 (B,k) for region_sum_l2_bwd_nhwc).  An index outside the map is skipped."""
+    flat_idx, F = _region_sum_args(fmap, flat_idx, kh, kw, "region_sum_l2_nhwc")
+    B, Cc, Hf, Wf = fmap.shape
+    k = flat_idx.size(1)
+    rows = torch.empty((B, F), device=fmap.device, dtype=torch.float32)
+    n2 = torch.empty((B, k), device=fmap.device, dtype=torch.float32)
+    sp = None
+    if shift is not None:
+        shift = _f32(shift, "shift")
+        if shift.numel() != F:
+            raise _lib.IsxError("region_sum_l2_nhwc: shift has %d elements, the rows %d" % (shift.numel(), F))
+        sp = shift.data_ptr()
+    check(lib().isx_region_sum_l2_nhwc(fmap.data_ptr(), B, Cc, Hf, Wf, kh, kw, flat_idx.data_ptr(), k, Wp, sp, eps, rows.data_ptr(), n2.data_ptr(),
+                                       _stream()), "isx_region_sum_l2_nhwc")
+    return rows, n2
+
+
+def region_sum_l2_bwd_nhwc(fmap, g, n2, kh, kw, flat_idx, Wp, add=None, add_every=1):
+    """Backward of region_sum_l2_nhwc (isx_region_sum_l2_bwd_nhwc): g (B, C*kh*kw) the gradient wrt the rows, n2 (B,k) as the forward wrote
+    it, add (channels-last (B / add_every, C, Hf, Wf)) or None: a further gradient of the map for every add_every-th image (0, add_every,
+    ...), added last.  Returns the channels-last (B,C,Hf,Wf) gradient."""
+    flat_idx, F = _region_sum_args(fmap, flat_idx, kh, kw, "region_sum_l2_bwd_nhwc")
+    B, Cc, Hf, Wf = fmap.shape
+    k = flat_idx.size(1)
+    g, n2 = _f32(g, "g"), _f32(n2, "n2")
+    if tuple(g.shape) != (B, F) or tuple(n2.shape) != (B, k):
+        raise _lib.IsxError("region_sum_l2_bwd_nhwc: g %s / n2 %s are not (%d, %d) / (%d, %d)" % (tuple(g.shape), tuple(n2.shape), B, F, B, k))
+    ap = None
+    if add is not None:
+        if add_every < 1 or B % add_every:
+            raise _lib.IsxError("region_sum_l2_bwd_nhwc: %d images do not split into groups of %d" % (B, add_every))
+        if not (add.is_cuda and add.dtype == torch.float32 and tuple(add.shape) == (B // add_every, Cc, Hf, Wf)
+                and add.permute(0, 2, 3, 1).is_contiguous()):
+            raise _lib.IsxError("region_sum_l2_bwd_nhwc: add must be a channels-last float32 CUDA tensor (%d, %d, %d, %d)" % (B // add_every, Cc, Hf, Wf))
+        _on_current_device(add, "add")
+        ap = add.data_ptr()
+    cw = torch.empty((B, k), device=fmap.device, dtype=torch.float32)
+    dx = torch.empty((B, Hf, Wf, Cc), device=fmap.device, dtype=torch.float32)
+    check(lib().isx_region_sum_l2_bwd_nhwc(fmap.data_ptr(), g.data_ptr(), n2.data_ptr(), B, Cc, Hf, Wf, kh, kw, flat_idx.data_ptr(), k, Wp, ap,
+                                           add_every if add is not None else 1, cw.data_ptr(), dx.data_ptr(), _stream()), "isx_region_sum_l2_bwd_nhwc")
+    return dx.permute(0, 3, 1, 2)
+
+
 def region_gather_l2(fmap, kh, kw, flat_idx, Wp, shift=None, eps=EPS):
     """Window gather + L2 + Shift.  fmap (C,Hf,Wf), flat_idx (k) -> rows (k,F); batched: fmap (B,C,Hf,Wf),
     flat_idx (B,k) -> rows (B,k,F)."""

@@ -83,11 +83,10 @@ def _convolutionalize_classifier(classifier, feature_size2d, has_reduc):
             seen += 1
 
 
-class TrunkHooks(nn.Module):
-    """What a net offers the training step (utils/train_general._Stepper) beyond forward(): its _SplitTrunk (`_trunk`: a plain attribute, so
-    it stays out of state_dict() and is copied by copy.deepcopy) and the hooks that need nothing but it and `features` -- trunk_precomputable,
-    precompute_trunk, suffix_engine and the gate of the tail engines.  What differs per net stays with the net: forward, forward_features,
-    head_rows, and which tail engine it has (head_engine / classif_head_engine: None here)."""
+class _TrunkBase(nn.Module):
+    """What the training step's contracts share: the net's _SplitTrunk (`_trunk`: a plain attribute, so it stays out of state_dict() and is
+    copied by copy.deepcopy) and the hooks that need nothing but it and `features` -- trunk_precomputable, precompute_trunk, suffix_engine and
+    the gate of the tail engines."""
     branches_are_scales = False     # (TuneClassifSub: True)
 
     def __init__(self):
@@ -153,10 +152,24 @@ class TrunkHooks(nn.Module):
             eng = self.__dict__[slot] = engine_class(self)
         return eng
 
+
+class TrunkHooks(_TrunkBase):
+    """What a net offers the training step (utils/train_general._Stepper) beyond forward(): _TrunkBase's hooks, and what differs per net and
+    stays with the net: forward, forward_features, head_rows, and which tail engine it has (head_engine / classif_head_engine: None here)."""
+
     def head_engine(self):
         return None
 
     def classif_head_engine(self):
+        return None
+
+
+class RegionHooks(_TrunkBase):
+    """The second contract: a net whose step is ALL OR NOTHING -- either its one engine (region_head_engine: everything behind the trunk,
+    both losses included) drives the whole step on precomputed prefix features, or the step takes the generic per-micro-batch route through
+    forward() and never asks for a hook.  (RegionDescriptorNet: its windows differ per image, so it has no forward_features / head_rows.)"""
+
+    def region_head_engine(self):
         return None
 
 
@@ -246,6 +259,8 @@ SUFFIX_ENGINE = os.environ.get("ISX_SUFFIX_ENGINE", "1") != "0"
 HEAD_ENGINE = os.environ.get("ISX_HEAD_ENGINE", "1") != "0"
 # A/B switch: ISX_CLASSIF_ENGINE=0 keeps pool + classifier + cross-entropy of a classification fine-tuning step on torch autograd, micro-batch by micro-batch.
 CLASSIF_ENGINE = os.environ.get("ISX_CLASSIF_ENGINE", "1") != "0"
+# A/B switch: ISX_REGION_ENGINE=0 keeps a region-descriptor training step on the generic route: the whole net on torch autograd, triplet by triplet.
+REGION_ENGINE = os.environ.get("ISX_REGION_ENGINE", "1") != "0"
 PREFIX_CACHE_BUDGET = int(os.environ.get("ISX_PREFIX_CACHE_GB", "96")) << 30      # HBM the prefix-feature cache of ONE resident set may take
 
 
@@ -570,7 +585,7 @@ class DescriptorNet(TrunkHooks):
         return _many(self.forward_single, xs)
 
 
-class RegionDescriptorNet(nn.Module):
+class RegionDescriptorNet(RegionHooks):
     def __init__(self, net, k, feature_dim, feature_size2d, untrained=-1):
         super().__init__()
         self.k = k
@@ -587,6 +602,17 @@ class RegionDescriptorNet(nn.Module):
         set_untrained_blocks([self.features, self.classifier], untrained)
         self.feature_reduc1 = _descriptor_head(in_features, self.feature_size)
         self.feature_reduc2 = NormalizeL2()
+
+    def region_head_engine(self):
+        """The libisx engine of everything behind the trunk for all local triplets of a training step at once (isx/region_head.py), when the
+        step may drive it by hand: the ResNets' tail, a head the head engine takes, GPU training with a precomputable trunk whose trainable part
+        (if any) runs on the suffix engine.  ISX_REGION_ENGINE=0: None (the step takes the generic route)."""
+        from isx.region_head import RegionHeadEngine
+        if not (REGION_ENGINE and self.trunk_precomputable() and RegionHeadEngine.applicable(self)):
+            return None
+        # the step decides its route BEFORE it computes any prefix features (all or nothing): the folded prefix is built (or found current) here
+        self._trunk._refresh(self.features, next(self.features.parameters()))
+        return self._tail_engine(REGION_ENGINE, "_region_head_engine", RegionHeadEngine)
 
     def _single_image(self, x, c):
         """x: (1,C,Hf,Wf) feature map, c: (1,n_cls,H',W') class-score map of ONE image."""

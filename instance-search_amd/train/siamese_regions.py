@@ -10,7 +10,7 @@ from model.siamese import RegionDescriptorNet, TuneClassifSub
 from model.custom_modules import TripletLoss
 from utils import (choose_rand_neg, choose_rand_neg_index, get_pos_couples, get_similarities, log, move_device, tensor,
                    test_print_descriptor, train_gen)
-from ._common import base_model, device_batch_size, fold_shape_buckets, label_index, load_weights, make_resident, scatter_rows, test_transform
+from ._common import base_model, device_batch_size, fold_shape_buckets, label_index, load_weights, make_resident, scatter_rows, stage_images, test_transform
 from .siamese_descriptor import mine_epoch_negatives, shuffle_couples
 from .siamese_regions_p import P
 
@@ -44,7 +44,10 @@ def get_siamese_net():
 train_type = 'Siamese sub-regions'
 
 
-def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, criterion2, optimizer, best_score=0):
+def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, criterion2, optimizer, best_score=0, one_shape=False):
+    """one_shape: every training image has the same shape (decided once, in main): create_batch then builds all the items it is given as
+    three stacks, which is what lets the training step compute the frozen trunk prefix of a whole mini-batch in one launch and run the rest on
+    isx/region_head.py; a set of mixed shapes keeps building one triplet per call."""
     trans = None if P.train_pre_proc else P.train_trans
     couples = get_pos_couples(train_set)
     log(P, '#pos (without order, with duplicates):{0}'.format(sum(len(c) for c in couples.values())))
@@ -57,12 +60,22 @@ def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, cr
         return [c + (k,) for c, k in zip(shuffled, negs)], {'epoch': epoch}
 
     def create_batch(batch, n, epoch):
-        # one triplet at a time (reference :95-137): the selected windows differ per image
-        lab, _, (im1, im2), k = batch[0]
-        im3 = train_set[k][0] if k >= 0 else choose_rand_neg(train_set, lab)
+        # one triplet at a time (reference :95-137): the selected windows differ per image.  A set of one image shape: all the items given,
+        # three (n, 3, H, W) stacks and (n,) labels -- the micro-batches of the generic route still come one triplet per call
         prep = (lambda im: im) if trans is None else trans
-        mv = lambda im: move_device(prep(im).unsqueeze(0), P.cuda_device)
-        return [mv(im1), mv(im2), mv(im3)], [move_device(torch.tensor([label_index(labels)[lab]], dtype=torch.int64), P.cuda_device)]
+        if not one_shape:
+            lab, _, (im1, im2), k = batch[0]
+            im3 = train_set[k][0] if k >= 0 else choose_rand_neg(train_set, lab)
+            mv = lambda im: move_device(prep(im).unsqueeze(0), P.cuda_device)
+            return [mv(im1), mv(im2), mv(im3)], [move_device(torch.tensor([label_index(labels)[lab]], dtype=torch.int64), P.cuda_device)]
+        a = stage_images([prep(im1) for _, _, (im1, _), _ in batch], P.cuda_device)
+        p = stage_images([prep(im2) for _, _, (_, im2), _ in batch], P.cuda_device)
+        ng = stage_images([prep(train_set[k][0] if k >= 0 else choose_rand_neg(train_set, lab)) for lab, _, _, k in batch], P.cuda_device)
+        ids = label_index(labels)
+        return [a, p, ng], [move_device(torch.tensor([ids[lab] for lab, _, _, _ in batch], dtype=torch.int64), P.cuda_device)]
+
+    # no random augmentation (negatives are drawn per epoch, in create_epoch): the training step may build mini-batches ahead of their turn
+    create_batch.deterministic = trans is None
 
     def create_loss(out, labels_list):
         # triplet loss on the descriptors + classification loss over the anchor's k windows (:139-150)
@@ -70,6 +83,10 @@ def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, cr
         cls_all = out[0][1].squeeze(0).t()                               # (k, num_classes)
         loss2 = criterion2(cls_all, labels_list[0].expand(cls_all.size(0)))
         return loss, loss2
+
+    # the declaration utils/train_general._Stepper._region_engine reads: the loss IS `criterion` on the three descriptors + `criterion2` over the
+    # anchor's selected windows, nothing else
+    create_loss.region_triplet = (criterion, criterion2)
 
     return train_gen(train_type, P, test_print_descriptor, get_embeddings, net, couples, testset_tuple, optimizer, create_epoch,
                      create_batch, create_loss, best_score=best_score)
@@ -90,7 +107,8 @@ def main(train_set, test_train_set, test_set):
     score = test_print_descriptor(train_type, P, net, testset_tuple, get_embeddings) if getattr(P, 'test_upfront', True) else 0
     if not getattr(P, 'train', True):
         return net, score
-    score = train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, criterion2, optimizer, best_score=score)
+    one_shape = len(set(tuple(getattr(im, 'shape', ())) for im, _, _ in train_set)) == 1 and hasattr(train_set[0][0], 'shape')
+    score = train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, criterion2, optimizer, best_score=score, one_shape=one_shape)
     test_print_descriptor(train_type, P, net, testset_tuple, get_embeddings, best_score=len(test_set) + 1)
     return net, score
 

@@ -100,10 +100,13 @@ class _Stepper(object):
     def __init__(self, P, net, make_batch, make_loss):
         from isx import dp
         from model.custom_modules import RowDeferredLinear
-        from model.siamese import TrunkHooks
+        from model.siamese import RegionHooks, TrunkHooks
         self.P, self.net, self.make_batch, self.make_loss = P, net, make_batch, make_loss
-        # a net without the training step's hooks (RegionDescriptorNet, any plain nn.Module) takes the generic per-micro-batch route
+        # a net without the training step's hooks (any plain nn.Module) takes the generic per-micro-batch route; so does a net of the second
+        # contract (RegionHooks: RegionDescriptorNet) whenever its one engine does not drive the whole step (_region_engine)
         self.hooked = isinstance(net, TrunkHooks)
+        self.region = isinstance(net, RegionHooks)
+        self._rhead_step = None                      # (engine or None,) while step() runs: _region_engine's answer for that step
         self.rank, self.world = _dp()
         mode = getattr(P, 'train_grad_exchange', 'tree')
         if mode not in ('tree', 'allreduce'):
@@ -177,8 +180,37 @@ class _Stepper(object):
         obj.backward()
         return obj.detach().reshape(-1)[0]           # a device scalar: the step reads the running loss back once, not per micro-batch
 
+    def _region_engine(self):
+        """The engine that drives a WHOLE step of a RegionHooks net (isx/region_head.py), or None: the generic route, bit for bit what it was.
+        All or nothing, decided before any prefix is computed and from what every rank knows: the script declared its losses
+        (`create_loss.region_triplet = (triplet criterion, window criterion)`), one triplet per micro-batch, tree mode, the batched route not
+        switched off, and the net's engine applies (ResNet tail, a head the head engine takes, frozen BatchNorm, GPU fp32)."""
+        if not self.region:
+            return None
+        if self._rhead_step is not None:             # inside step(): decided once, at its start
+            return self._rhead_step[0]
+        P = self.P
+        if not (self.mode == 'tree' and P.train_micro_batch == 1 and getattr(P, 'train_suffix_batched', True)
+                and getattr(P, 'train_trunk_per_minibatch', True) and getattr(self.make_loss, 'region_triplet', None) is not None):
+            return None
+        return self.net.region_head_engine()
+
+    def _region_fits(self, rhead, feats):
+        """From the shapes alone: three branches of one shape whose trunk output holds at least k windows (a shorter score map makes the
+        reference's cls_out carry zero columns: generic route)."""
+        if len(feats) != 3 or len(set(tuple(f.shape[1:]) for f in feats)) != 1:
+            return False
+        h, w = feats[0].shape[2], feats[0].shape[3]
+        eng = self.net.suffix_engine()
+        for convs, _ in (eng.layers if eng is not None else ()):
+            s = convs[1].stride
+            h, w = (h - 1) // s + 1, (w - 1) // s + 1
+        return rhead.fits(h, w)
+
     def _prefix_ok(self, n_leaves):
         """May the frozen trunk prefix be computed outside the micro-batches this step?"""
+        if self.region:
+            return bool(n_leaves >= 1 and self._region_engine() is not None)
         return bool(self.hooked and getattr(self.P, 'train_trunk_per_minibatch', True) and n_leaves >= 1 and self.net.trunk_precomputable())
 
     def _precompute(self, local, n_leaves, batch_args):
@@ -189,7 +221,8 @@ class _Stepper(object):
         rng_state = random.getstate()
         inputs, targets = self.make_batch(local, len(local), **batch_args)
         feats = self.net.precompute_trunk(*inputs, cache=bool(getattr(self.P, 'train_prefix_cache', False)))
-        if feats is None:                            # (CPU tensors, ragged shapes): the batch is built again per micro-batch, from the same random state
+        if feats is None or (self.region and not self._region_fits(self._region_engine(), feats)):
+            # (CPU tensors, ragged shapes, a region net's map shorter than k windows): the batch is built again per micro-batch, from the same random state
             random.setstate(rng_state)
             return None
         return feats, targets
@@ -312,11 +345,46 @@ class _Stepper(object):
                 flat_all += part
         return flat_all, list(total.unbind(0))
 
+    def _regions_batched(self, eng, rhead, mini_size, pre, sink, mine, offsets):
+        """Region-descriptor siamese training whose script declared its losses (train/siamese_regions.py, `create_loss.region_triplet =
+        (criterion, criterion2)`: the triplet criterion on the three region descriptors + criterion2 over the ANCHOR's k selected windows,
+        reference :139-150), one triplet per leaf: all local leaves through the trunk suffix (isx/suffix.py), everything behind it with both
+        losses (isx/region_head.py) and the suffix backward, gradients kept apart per leaf as in _leaves_batched.  A leaf's loss is _objective's
+        formula on its two per-leaf sums.  Returns (flat_all (L, total), losses)."""
+        P = self.P
+        feats, targets_all = pre
+        L = len(mine)
+        share = 1.0 / float(mini_size)
+        trip, xent = self.make_loss.region_triplet
+        k = rhead.k
+        flat_all = self._flat_all(L)
+        y_all, saved = self._suffix_forward(eng, feats, offsets, 1)
+        labels = torch.cat([targets_all[0][o:o + 1] for o in offsets], 0)
+        with _phase("heads"):
+            scale_a, scale_b, rescale = self._leaf_scales(trip, 1, share)
+            mean2 = xent.reduction == 'mean'
+            shard = sink.shard_for(rhead.lin.weight) if sink is not None else None
+            per_t, per_x, dy_all, _ = rhead.step(y_all, labels, L, trip, (scale_a, scale_b),
+                                                 ((1.0 / k) if mean2 else 1.0, P.train_loss2_alpha * (share if P.train_loss2_avg else 1.0)),
+                                                 sink, flat_all, self.flat.slices, shard=shard,
+                                                 leaf_ids=list(sink.leaf_ids) if shard is not None else None)
+            loss2 = per_x / k if mean2 else per_x
+            losses = rescale(per_t) + P.train_loss2_alpha * (loss2 * share if P.train_loss2_avg else loss2)
+        self._suffix_backward(eng, saved, dy_all, L, flat_all)
+        return flat_all, list(losses.unbind(0))
+
     def _route(self, mine, n, mb, pre, sink):
         """The batched route of this step: a callable (leaves, their row offsets) -> (flat_all: one flat gradient row per leaf, losses), or
         None for the generic route (one _forward_backward per micro-batch)."""
         # batched engines need equal micro-batches; decided from the MINI-BATCH (n % mb == 0: every leaf of every rank has mb triplets), not from
         # this rank's leaves, so that every rank and the single-process run take the same numeric path (round-4 ADVICE)
+        if self.region:
+            # all or nothing: `pre` exists only where _region_engine and _region_fits said yes (_prefix_ok, _precompute)
+            rhead = self._region_engine() if (pre is not None and mine) else None
+            if rhead is None:
+                return None
+            import functools
+            return functools.partial(self._regions_batched, self.net.suffix_engine(), rhead, n, pre, sink)
         if not (self.hooked and self.mode == 'tree' and pre is not None and mine and n % mb == 0):
             return None
         # a net whose branches are the SCALES of an image (TuneClassifSub: feature maps of different size per branch) takes the
@@ -381,8 +449,8 @@ class _Stepper(object):
             items = [t for g in groups for t in g]
             inputs, targets = self.make_batch(items, len(items), **batch_args)
             feats = self.net.precompute_trunk(*inputs)
-            if feats is None:
-                self._epoch_set = None           # CPU tensors / ragged shapes: the steps build their own batches
+            if feats is None or (self.region and not self._region_fits(self._region_engine(), feats)):
+                self._epoch_set = None           # CPU tensors / ragged shapes / too short a map for a region net: the steps build their own batches
                 return None
             a = self._ahead = (start, len(groups), len(groups[0]), feats, targets, len(items))
         g, m = (start - a[0]) // n, a[2]
@@ -393,6 +461,15 @@ class _Stepper(object):
         return feats, targets
 
     def step(self, optimizer, mini_batch, batch_args, start=None):
+        # the route of a region net is decided ONCE per step (the engine's gate walks every prefix parameter): the look-ahead, the prefix and
+        # the route below all read this answer
+        self._rhead_step = (self._region_engine(),) if self.region else None
+        try:
+            return self._step(optimizer, mini_batch, batch_args, start)
+        finally:
+            self._rhead_step = None
+
+    def _step(self, optimizer, mini_batch, batch_args, start):
         from isx import dp
         P, n = self.P, len(mini_batch)
         mb = P.train_micro_batch if 0 < P.train_micro_batch < n else n
