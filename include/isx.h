@@ -101,6 +101,42 @@ int isx_bias_act_inplace(float* y, const float* bias, const float* residual, int
 int isx_images_u8_to_f32(const uint8_t* img, int64_t B, int H, int W, float mean0, float mean1, float mean2, float std0, float std1,
                          float std2, int channels_last, float* out, isx_stream_t stream);
 
+/* Training-time augmentation (reference utils/image.py:128-187 random_affine_noisy_cv, the train_trans of every train/(name)_p.py; csrc/augment.hip):
+ * per image an affine warp through cubic B-spline interpolation -- scipy.ndimage.affine_transform(order 3, mode 'constant') per channel, as
+ * affine_cv calls it --, the reference's uint8 cast, random bytes where the warp leaves the input, then ToTensor + Normalize.
+ *   img        (N,H,W,3) uint8, the resident set; image b of the call is row rows[b] of it (rows == NULL: rows 0 .. B-1).  Row numbers are
+ *              trusted: they are read on the device, the call cannot check them against N
+ *   mat        (B,6) fp64: m00 m01 t0 m10 m11 t1; output pixel (y, x) reads the input at (yi, xi) = (t0 + m00 y + m01 x, t1 + m10 y + m11 x)
+ *   out_u8     (B,H,W,3) uint8 or NULL;  out_f32  fp32, (B,3,H,W) memory or channels-last ((B,H,W,3)) memory, or NULL; at least one of them
+ *   mean, std  3 floats each in device memory, or NULL (0 and 1)
+ *   ws         isx_affine_noisy_workspace(B, H, W) bytes: the fp64 spline coefficients, (B,H,W,3), rounded up to 256 bytes
+ * Arithmetic, all fp64, one rounding per operation (no contraction: `#pragma clang fp contract(off)` in the source), IEEE division:
+ *   prefilter  per channel the recursive cubic B-spline filter along axis 0 (lines of length H), then along axis 1, pole z = sqrt(3) - 2.  Per
+ *              line of n > 1 values: c *= (1 - z)(1 - 1/z);  c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1..n-2} z^i (c[i] + z^(n-1) c[n-1-i])) /
+ *              (1 - z^(n-1) z^(n-1)), terms added in order of i, the sum stopped before the first i with |z^i| < 1e-30, powers of z by repeated
+ *              multiplication;  c[i] = c[i] + z c[i-1] upwards;  c[n-1] = (z c[n-2] + c[n-1]) (z / (z z - 1));  c[i] = z (c[i+1] - c[i]) downwards
+ *   warp       OUTSIDE iff yi < 0 || yi > H-1 || xi < 0 || xi > W-1 (or NaN).  Otherwise taps floor-1 .. floor+2 per axis, indices mirrored at 0
+ *              and n-1; with t = v - floor(v), u = 1 - t:  w1 = (t t (t-2) 3 + 4)/6, w2 = (u u (u-2) 3 + 4)/6, w0 = u u u / 6, w3 = 1 - w0 - w1 - w2;
+ *              value = sum over (row tap j, column tap k), j major, of (c[j][k] wy[j]) wx[k], from 0.0
+ *   cast       truncate toward zero to a 64-bit integer, then modulo 256 (what the reference's astype(np.uint8) does: -34.37 -> 222,
+ *              273.2 -> 17); cubic overshoot wraps, it is not clamped
+ *   noise      channel c of an OUTSIDE pixel (y, x) of image b is ISX_NOISE_BYTE(seed, noise_ids[b] * 3HW + 3 (y W + x) + c), arithmetic modulo
+ *              2^64: a pure function of (seed, noise id, y, x, c) -- never of B, the launch geometry or the other images of the call.  (The
+ *              reference draws these bytes from np.random in raster order; that stream is not reproduced.)
+ *   normalise  out_f32 = ((float)u8 / 255.0f - mean[c]) / std[c]: bit for bit isx_images_u8_to_f32 on out_u8
+ * Refused: 3 H W >= 2^31, B > 65535, a row of 3 W fp64 values beyond 64 KiB, ws or out_f32 off a 16-byte boundary, mat / rows / noise_ids off
+ * an 8-byte boundary, a workspace that is too small (ISX_ERR_WORKSPACE).  isx_affine_noisy_workspace returns 0 for a shape it refuses. */
+#define ISX_NOISE_MIX1(z) (((z) ^ ((z) >> 30)) * 0xBF58476D1CE4E5B9ull)
+#define ISX_NOISE_MIX2(z) (((z) ^ ((z) >> 27)) * 0x94D049BB133111EBull)
+#define ISX_NOISE_MIX3(z) ((z) ^ ((z) >> 31))
+/* splitmix64's output function on seed + golden ratio * counter; the byte is the top one */
+#define ISX_NOISE_BYTE(seed, counter) \
+    ((uint8_t)(ISX_NOISE_MIX3(ISX_NOISE_MIX2(ISX_NOISE_MIX1((uint64_t)(seed) + 0x9E3779B97F4A7C15ull * (uint64_t)(counter)))) >> 56))
+size_t isx_affine_noisy_workspace(int64_t B, int H, int W);
+int isx_affine_noisy_u8(const uint8_t* img, const int64_t* rows, int64_t B, int H, int W, const double* mat, uint64_t seed,
+                        const int64_t* noise_ids, const float* mean, const float* std, int channels_last, uint8_t* out_u8, float* out_f32,
+                        void* ws, size_t ws_bytes, isx_stream_t stream);
+
 /* Stem of the same trunk: relu(conv7x7 + bias) -> MaxPool2d(3, stride 2, padding 1) (torchvision ResNet stem as split
  * by model/nn_utils.py:56-71), epilogue and pooling in ONE pass over the channels-last convolution output:
  * out[b][ho][wo][c] = relu(max_{3x3 window, in bounds} y[b][2ho-1+kh][2wo-1+kw][c] + bias[c]).

@@ -197,6 +197,71 @@ def images_u8_to_f32(img_u8, mean, std, channels_last=True):
     return out
 
 
+AFFINE_WORKSPACE_BUDGET = 1 << 30      # bytes of fp64 spline coefficients per launch of affine_noisy (24 bytes per pixel); larger batches go in chunks
+_MEAN_STD = {}
+
+
+def _mean_std_device(mean, std, device):
+    """(6,) fp32 device tensor mean | std, cached per (values, device): the kernel reads them from device memory."""
+    key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), device)
+    t = _MEAN_STD.get(key)
+    if t is None:
+        if len(key[0]) != 3 or len(key[1]) != 3 or 0.0 in key[1]:
+            raise _lib.IsxError("mean and std must be three values each, std non-zero")
+        _MEAN_STD.clear()
+        t = _MEAN_STD[key] = torch.tensor(key[0] + key[1], dtype=torch.float32, device=device)
+    return t
+
+
+def affine_noisy(img_u8, rows, mats, seed, noise_ids, mean, std, channels_last=True, want_u8=False):
+    """The reference's random_affine_noisy_cv + ToTensor + Normalize for a batch (isx_affine_noisy_u8): image b is row rows[b] of the
+    (N,H,W,3) uint8 set `img_u8` (rows None: rows 0 .. B-1), warped by mats[b] = (m00, m01, t0, m10, m11, t1) (fp64), outside pixels filled with
+    the noise of (seed, noise_ids[b]).  Returns the normalised (B,3,H,W) fp32 batch (channels-last memory by default), or (that, the warped
+    (B,H,W,3) uint8 images) with want_u8.  mats / noise_ids / rows may be host arrays; they are copied to the device."""
+    if not (img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 4 and img_u8.shape[3] == 3 and img_u8.is_contiguous()):
+        raise _lib.IsxError("img_u8 must be a contiguous (N,H,W,3) uint8 CUDA tensor")
+    _on_current_device(img_u8, "img_u8")
+    dev = img_u8.device
+    N, H, W, _ = img_u8.shape
+    mats = torch.as_tensor(mats, dtype=torch.float64).reshape(-1, 6)
+    B = mats.shape[0]
+    noise_ids = torch.as_tensor(noise_ids, dtype=torch.int64).reshape(-1)
+    if rows is not None:
+        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+    if not (mats.is_cuda or noise_ids.is_cuda or (rows is not None and rows.is_cuda)):
+        # host parameters: ONE pinned block and one asynchronous copy for the three arrays (three pageable copies would each block the host)
+        parts = [mats.contiguous().view(torch.int64).reshape(-1), noise_ids] + ([rows] if rows is not None else [])
+        packed = torch.cat(parts).pin_memory().to(dev, non_blocking=True)
+        mats, noise_ids = packed[:6 * B].view(torch.float64).view(B, 6), packed[6 * B:6 * B + noise_ids.numel()]
+        rows = packed[6 * B + noise_ids.numel():] if rows is not None else None
+    else:
+        mats, noise_ids = mats.to(dev).contiguous(), noise_ids.to(dev).contiguous()
+        rows = rows.to(dev).contiguous() if rows is not None else None
+    if noise_ids.numel() != B or (rows is not None and rows.numel() != B) or (rows is None and B > N):
+        raise _lib.IsxError("affine_noisy: %d matrices, %d noise ids, %s rows, %d images" % (B, noise_ids.numel(), "no" if rows is None else rows.numel(), N))
+    ms = _mean_std_device(mean, std, dev)
+    out = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32, memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    u8 = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8) if want_u8 else None
+    if B == 0:
+        return (out, u8) if want_u8 else out
+    L = lib()
+    per_image = int(L.isx_affine_noisy_workspace(1, H, W))
+    if per_image == 0:
+        raise _lib.IsxError("affine_noisy: images of %d x %d are refused (isx_affine_noisy_workspace)" % (H, W))
+    chunk = int(max(1, min(B, 65535, AFFINE_WORKSPACE_BUDGET // per_image)))
+    ws_bytes = int(L.isx_affine_noisy_workspace(chunk, H, W))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out_flat = out.permute(0, 2, 3, 1) if channels_last else out                       # a view whose dim 0 slices are contiguous memory
+    seed = int(seed) & (2 ** 64 - 1)
+    for s in range(0, B, chunk):
+        n = min(chunk, B - s)
+        check(L.isx_affine_noisy_u8(img_u8.data_ptr() if rows is not None else img_u8[s:].data_ptr(), None if rows is None else rows[s:].data_ptr(), n, H, W,
+                                    mats[s:].data_ptr(), seed, noise_ids[s:].data_ptr(), ms.data_ptr(), ms[3:].data_ptr(), 1 if channels_last else 0,
+                                    None if u8 is None else u8[s:].data_ptr(), out_flat[s:].data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+              "isx_affine_noisy_u8")
+    return (out, u8) if want_u8 else out
+
+
 # Optional per-launch timing of the trunk kernels (bench.py): a list that receives
 # (kernel, algorithmic FLOP, algorithmic bytes, start event, end event) per call; None = off.
 KERNEL_TIMER = None

@@ -210,6 +210,14 @@ class ResidentImages(object):
         x._isx_rows = (self, idx)               # provenance: lets a frozen trunk prefix look its features up instead of recomputing them
         return x
 
+    def augmented(self, ims, mats, seed, noise_ids):
+        """The network input of `ims` under the augmentation (mats, seed, noise_ids): ONE isx_affine_noisy_u8 call that reads the resident
+        uint8 set through the row numbers -- no index_select copy, no separate normalise.  The result is new pixels, not rows of the set: it
+        carries no `_isx_rows` provenance (no prefix-feature cache, no look-ahead for augmented batches)."""
+        from isx import ops
+        idx = torch.tensor([self.index[id(im)] for im in ims], dtype=torch.int64)           # host: copied with the other parameters, one copy
+        return ops.affine_noisy(self.data, idx, mats, seed, noise_ids, RAW_INGEST["mean"], RAW_INGEST["std"], channels_last=True)
+
     def normalised_rows(self, rows):
         """The network input of the given rows of the set (fp32, normalised)."""
         x = self.data.index_select(0, rows)
@@ -239,9 +247,49 @@ def drop_resident():
     del _RESIDENT[:]
 
 
-def stage_images(ims, device):
-    """A list of same-shaped image tensors (fp32 CHW, or uint8 HWC for the raw ingest) -> one device batch, normalised."""
+def is_augmenter(trans):
+    """Is `trans` the reference's training augmentation (utils.image.random_affine_noisy_cv)?  The training mains then run it per batch on the
+    device instead of calling it image by image on the host."""
+    from utils.image import RandomAffineNoisy
+    return isinstance(trans, RandomAffineNoisy)
+
+
+def augment_keys(seed, epoch, positions, role):
+    """One key row per image of a batch: (P.train_seed, epoch, position of the item in the epoch's list, role of the image in the item).  The
+    parameters and the noise of an image are a function of its key alone (RandomAffineNoisy.plan), not of a running stream: a data-parallel
+    rank that builds only its slice of a mini-batch draws what the single process draws for those images."""
+    return np.array([[int(seed or 0), int(epoch), int(p), int(role)] for p in positions], dtype=np.int64).reshape(-1, 4)
+
+
+def _stage_augmented(ims, device, augmenter, keys, seed):
+    first = ims[0]
+    if any(im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.shape != first.shape for im in ims):
+        raise RuntimeError("augmentation needs raw same-sized (H,W,3) uint8 images (P.train_pre_proc = False keeps the training set raw)")
+    if RAW_INGEST["mean"] is None:
+        raise RuntimeError("uint8 images in the dataset but no mean/std registered (train._common.RAW_INGEST)")
+    H, W = int(first.shape[0]), int(first.shape[1])
+    mats, noise_ids = augmenter.plan(keys, H, W)
+    seed = int(seed or 0)
+    if device >= 0:
+        from isx import ops
+        for r in _RESIDENT:
+            if r.covers(ims):
+                return r.augmented(ims, mats, seed, noise_ids)
+        x = torch.stack(ims, 0)
+        x = x if x.is_cuda else x.pin_memory().cuda(non_blocking=True)
+        return ops.affine_noisy(x.contiguous(), None, mats, seed, noise_ids, RAW_INGEST["mean"], RAW_INGEST["std"], channels_last=True)
+    from utils.image import affine_noisy
+    x = torch.from_numpy(np.stack([affine_noisy(im.numpy(), mats[b], seed, int(noise_ids[b])) for b, im in enumerate(ims)]))
+    return normalise_u8_batch(x, device)
+
+
+def stage_images(ims, device, augment=None):
+    """A list of same-shaped image tensors (fp32 CHW, or uint8 HWC for the raw ingest) -> one device batch, normalised.
+    augment = (augmenter, keys, seed): the raw uint8 images go through the augmenter first (utils.image.RandomAffineNoisy; keys from
+    augment_keys) -- on the GPU one isx_affine_noisy_u8 call, on the CPU the numpy twin image by image."""
     ims = resolve_images(ims)
+    if augment is not None:
+        return _stage_augmented(ims, device, *augment)
     if device >= 0:
         for r in _RESIDENT:
             if r.covers(ims):
@@ -429,21 +477,56 @@ def load_training_sets(P, dataset_full, labels):
     `<dataset_full>/test` whose label is known are the queries.  With images pre-processed once and nothing augmented (P.train_pre_proc, the
     reference's setting: train_trans == test_trans) the training and the gallery set are the same tensors -- one list serves as both (the
     reference keeps two copies).  The dataset-dependent fields of P (reference train/*_p.py:27-48) are filled from the dataset id.  On the GPU
-    the sets carry raw uint8 pixels (normalised on the device), decoded by the processes of train/_decode_farm.py."""
+    the sets carry raw uint8 pixels (normalised on the device), decoded by the processes of train/_decode_farm.py.  With the reference's augmentation
+    (P.train_pre_proc = False, P.train_trans = utils.image.random_affine_noisy_cv(...)) the sets are raw uint8 on every device and still one list:
+    the training mains warp a batch's images when they build it, the evaluations normalise the same images as they are."""
     from test import _common as C
     from .global_p import feature_sizes, image_sizes
     dataset_id = C.dataset_id_of(dataset_full)
-    if not getattr(P, 'train_pre_proc', True) or getattr(P, 'train_trans', None) is not None:
-        raise NotImplementedError("training entry point: only pre-processed, un-augmented training sets (P.train_pre_proc = True, P.train_trans = None); "
-                                  "build augmented sets yourself and call main(train_set, test_train_set, test_set)")
+    pre_proc, trans = getattr(P, 'train_pre_proc', True), getattr(P, 'train_trans', None)
+    augmented = not pre_proc and is_augmenter(trans)
+    if not augmented and (not pre_proc or trans is not None):
+        raise NotImplementedError("training entry point: pre-processed, un-augmented training sets (P.train_pre_proc = True, P.train_trans = None) or the "
+                                  "reference's augmentation (P.train_pre_proc = False, P.train_trans = utils.image.random_affine_noisy_cv(...)); "
+                                  "build other sets yourself and call main(train_set, test_train_set, test_set)")
     del labels[:]
-    test_set, ref_set = C.load_sets(dataset_full, labels, raw=(P.cuda_device >= 0), lazy=False)
+    # augmented: the training set stays RAW uint8 on every device (the augmenter warps bytes; ToTensor + Normalize follow it), and it is still the
+    # gallery of the evaluations -- one list, normalised un-augmented there
+    test_set, ref_set = C.load_sets(dataset_full, labels, raw=(P.cuda_device >= 0 or augmented), lazy=False)
+    if augmented and C.is_synthetic(dataset_full):
+        test_set, ref_set = _raw_u8_set(test_set), _raw_u8_set(ref_set)
     P.dataset_full, P.dataset_id = dataset_full, dataset_id
     P.image_input_size = image_sizes[dataset_id]
     P.num_classes = len(labels)
     P.feature_size2d = feature_sizes[str(P.cnn_model).lower(), image_sizes[dataset_id]]
     P.test_pre_proc = True
     return ref_set, ref_set, test_set
+
+
+def _raw_u8_set(dataset):
+    """A synthetic set (normalised fp32 CHW tensors, utils.dataset.synthetic_image_set) as raw (H,W,3) uint8 images, mean/std registered for the
+    ToTensor + Normalize that follows the augmenter."""
+    from utils.dataset import IMAGENET_MEAN, IMAGENET_STD
+    RAW_INGEST["mean"], RAW_INGEST["std"] = list(IMAGENET_MEAN), list(IMAGENET_STD)
+    m, s_ = torch.tensor(IMAGENET_MEAN).view(3, 1, 1), torch.tensor(IMAGENET_STD).view(3, 1, 1)
+    return [((im * s_ + m).mul(255.0).round().clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous(), lab, path) for im, lab, path in dataset]
+
+
+def parse_augment(arg):
+    """'reference' -> the augmenter of the reference's train/*_p.py (rotation 45, no shift, scales .25, flip); 'rot,hr,vr,hsr,vsr,hflip' -> that
+    one (degrees, four ratios, 0 / 1); 'off' -> None."""
+    from utils.image import random_affine_noisy_cv
+    if arg in ('off', 'none', ''):
+        return None
+    if arg == 'reference':
+        return random_affine_noisy_cv(rotation=45, h_range=0, v_range=0, hs_range=.25, vs_range=.25, h_flip=True)
+    v = arg.split(',')
+    if len(v) != 6 or v[5].strip() not in ('0', '1'):
+        raise ValueError("--augment takes 'reference', 'off' or rot,hr,vr,hsr,vsr,hflip (hflip 0 or 1), got %r" % (arg,))
+    rot, hr, vr, hsr, vsr = [float(x) for x in v[:5]]
+    if min(rot, hr, vr, hsr, vsr) < 0 or max(hsr, vsr) >= 1:
+        raise ValueError('--augment: ranges are non-negative and the scale ranges below 1, got %r' % (arg,))
+    return random_affine_noisy_cv(rotation=rot, h_range=hr, v_range=vr, hs_range=hsr, vs_range=vsr, h_flip=(v[5].strip() == '1'))
 
 
 def parse_scales(arg):
@@ -461,8 +544,9 @@ def parse_scales(arg):
 
 def training_cli(argv, P, run, what):
     """`python -m train.<approach> --dataset=<folder | synthetic:...> [--model=] [--device=] [--epochs=] [--classif-model=] [--preload-net=]
-    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=] [--bn-model=] [--scales=]`
-    (--scales: comma list of shorter-side sizes of train.classif_regions, 0 = the image as is): the reference's training scripts take everything from their
+    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=] [--bn-model=] [--scales=] [--augment=]`
+    (--scales: comma list of shorter-side sizes of train.classif_regions, 0 = the image as is; --augment=reference | rot,hr,vr,hsr,vsr,hflip: the
+    reference's random_affine_noisy_cv on every training image of every batch, default off): the reference's training scripts take everything from their
     *_p.py file (edit and run); the same fields can be given here instead."""
     import getopt
     import sys
@@ -470,7 +554,7 @@ def training_cli(argv, P, run, what):
             'classif-model': ('classif_model', str), 'preload-net': ('preload_net', str), 'save-dir': ('save_dir', str),
             'feature-dim': ('feature_dim', int), 'batch-size': ('train_batch_size', int), 'micro-batch': ('train_micro_batch', int),
             'lr': ('train_lr', float), 'seed': ('train_seed', int), 'loss-int': ('train_loss_int', int), 'bn-model': ('bn_model', str),
-            'scales': ('train_sub_scales', parse_scales)}
+            'scales': ('train_sub_scales', parse_scales), 'augment': ('train_trans', parse_augment)}
     try:
         opts, _ = getopt.getopt(argv, '', ['help'] + [k + '=' for k in spec])
     except getopt.GetoptError as e:
@@ -483,6 +567,8 @@ def training_cli(argv, P, run, what):
         field, typ = spec[opt[2:]]
         try:
             setattr(P, field, typ(arg))
+            if field == 'train_trans':
+                P.train_pre_proc = P.train_trans is None      # the augmenter works on the raw training set (reference train/*_p.py: train_pre_proc = False)
         except ValueError as e:
             print('%s=%s: %s\nusage: python -m %s %s' % (opt, arg, e, what, ' '.join('[--%s=]' % k for k in spec)))
             sys.exit(2)

@@ -108,9 +108,11 @@ def get_class_net():
 def train_classif(net, train_set, testset_tuple, criterion, optimizer, best_score=0):
     """Fine-tune `net` as a classifier of the instance labels (reference :53-78): per epoch the training set is shuffled, a batch is the image
     rows + the label indices, the loss is `criterion` on the class scores."""
+    from ._common import augment_keys, is_augmenter
     trans = None if P.train_pre_proc else P.train_trans
-    if trans is None:
-        make_resident(train_set, P.cuda_device)          # batches become row gathers on the device
+    aug = trans if is_augmenter(trans) else None        # the reference's random_affine_noisy_cv: one kernel call per batch, not a host callable per image
+    if trans is None or aug is not None:
+        make_resident(train_set, P.cuda_device)          # batches become row gathers on the device (augmented: the warp reads the resident rows)
     ids = label_index(labels)
     unknown = sorted(set(lab for _, lab, _ in train_set if lab not in ids))
     if unknown:
@@ -121,9 +123,17 @@ def train_classif(net, train_set, testset_tuple, criterion, optimizer, best_scor
     def create_epoch(epoch, train_set, testset_tuple):
         shuffled = list(train_set)                       # the caller's list keeps its order (it may double as the evaluation gallery)
         random.shuffle(shuffled)
+        if aug is not None:
+            # an image's augmentation is keyed on (P.train_seed, epoch, the item's place in the epoch's list): the same on every rank
+            return [item + (i,) for i, item in enumerate(shuffled)], {'epoch': epoch}
         return shuffled, {}
 
-    def create_batch(batch, n):
+    def create_batch(batch, n, epoch=None):
+        if aug is not None:
+            keys = augment_keys(P.train_seed, epoch, [item[3] for item in batch], 0)
+            x = stage_images([item[0] for item in batch], P.cuda_device, augment=(aug, keys, P.train_seed))
+            ids = label_index(labels)
+            return [x], [move_device(torch.tensor([ids[item[1]] for item in batch], dtype=torch.int64), P.cuda_device)]
         prep = (lambda im: im) if trans is None else trans
         x = stage_images([prep(im) for im, _, _ in batch], P.cuda_device)
         ids = label_index(labels)

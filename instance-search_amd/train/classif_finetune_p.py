@@ -1,6 +1,7 @@
-"""Parameters of the classification fine-tuning (reference train/classif_finetune_p.py:53-99).  The reference's cv2 augmentation
-(random_affine_noisy_cv) is not part of this package: the training images are pre-processed once (train_pre_proc = True), and a
-user-supplied P.train_trans callable is applied on the host when set (main() on sets you loaded yourself).  train_bn: the reference enables
+"""Parameters of the classification fine-tuning (reference train/classif_finetune_p.py:53-99).  The reference's augmentation
+(random_affine_noisy_cv) is OFF by default: the training images are pre-processed once (train_pre_proc = True).  --augment=reference (or
+train_pre_proc = False with P.train_trans = utils.image.random_affine_noisy_cv(...)) runs it per batch on the device; any other
+user-supplied P.train_trans callable is applied on the host (main() on sets you loaded yourself).  train_bn: the reference enables
 BatchNorm learning for batches >= 16; here it stays off by default (the frozen-BatchNorm step runs on the HIP engines), set it to True for
 the reference's behaviour on torch autograd."""
 from .params import Params

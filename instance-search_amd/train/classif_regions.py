@@ -216,7 +216,11 @@ def run(dataset_full=None):
     """The reference's main() (:152-200): the sets come from P.dataset_full (a dataset folder with its `test` sub-folder, or a `synthetic:` spec),
     every training image at the scales of P.train_sub_scales (None: as is, an int: shorter side to that size; reference classif_regions_p.py:
     [identity, scale_cv(224)])."""
-    from ._common import load_training_sets
+    from ._common import is_augmenter, load_training_sets
+    if is_augmenter(getattr(P, 'train_trans', None)):
+        # the reference's per-scale transform lists put a resize (scale_cv) AFTER the warp: the augmenter kernel has no such stage
+        raise NotImplementedError('train.classif_regions: augmentation is not supported here -- the per-scale transform lists of the reference '
+                                  '(classif_regions_p.py) resize after the warp, which isx_affine_noisy_u8 does not do; run with --augment=off')
     train_set, test_train_set, test_set = load_training_sets(P, dataset_full or P.dataset_full, labels)
     scales = list(getattr(P, 'train_sub_scales', None) or [None, 224])
     return main(multi_scale_items(train_set, scales), test_train_set, test_set)

@@ -80,6 +80,15 @@ class Params(object):
         self.train_test_int = 0
         self.train_pre_proc = True
         self.train_trans = None
+        # the reference's augmentation (train/*_p.py: train_aug_rot .. train_aug_hflip feed random_affine_noisy_cv, the head of train_trans).  OFF by
+        # default here: P.train_pre_proc = False and P.train_trans = utils.image.random_affine_noisy_cv(...) -- or --augment= on the command
+        # line -- switch it on; these fields only carry the reference's values for whoever builds that augmenter from P
+        self.train_aug_rot = 45
+        self.train_aug_hrange = 0
+        self.train_aug_vrange = 0
+        self.train_aug_hsrange = .25
+        self.train_aug_vsrange = .25
+        self.train_aug_hflip = True
         self.triplet_margin = 0.1
         self.train_epoch_switch = 2          # semi-hard negatives before this epoch, hard ones after
         self.save_dir = None

@@ -13,7 +13,8 @@ from model.siamese import DescriptorNet, TuneClassif
 from model.custom_modules import TripletLoss
 from utils import (choose_rand_neg, choose_rand_neg_index, embeddings_device_dim, fold_batches, get_pos_couples, get_similarities, log, move_device,
                    tensor, test_print_descriptor, train_gen)
-from ._common import BatchStager, base_model, device_batch_size, label_index, load_weights, make_resident, stage_batch, stage_images, test_transform
+from ._common import (BatchStager, augment_keys, base_model, device_batch_size, is_augmenter, label_index, load_weights, make_resident, stage_batch,
+                      stage_images, test_transform)
 from .siamese_descriptor_p import P
 
 labels = []
@@ -99,8 +100,9 @@ def _mine_block(similarities, lab, i1, i2, semi_hard, row_base):
 
 def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, optimizer, best_score=0):
     trans = None if P.train_pre_proc else P.train_trans
-    if trans is None:
-        make_resident(train_set, P.cuda_device)          # batches become row gathers on the device
+    aug = trans if is_augmenter(trans) else None        # the reference's random_affine_noisy_cv: one kernel call per batch, not a host callable per image
+    if trans is None or aug is not None:
+        make_resident(train_set, P.cuda_device)          # batches become row gathers on the device (augmented: the warp reads the resident rows)
     couples = get_pos_couples(train_set)
     log(P, '#pos (without order, with duplicates):{0}'.format(sum(len(c) for c in couples.values())))
 
@@ -115,9 +117,23 @@ def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, op
         # data-parallel rank holds the same list, whatever slice of the mini-batches it will run
         negs = [k if k >= 0 else choose_rand_neg_index(train_set, c[0]) for c, k in zip(shuffled, negs)]
         tagged = [c + (k,) for c, k in zip(shuffled, negs)]
+        if aug is not None:
+            tagged = [c + (i,) for i, c in enumerate(tagged)]       # the item's place in the epoch: what its images' augmentation is keyed on
         return tagged, {'epoch': epoch}
 
     def create_batch(batch, n, epoch):
+        if aug is not None:
+            # parameters and noise of an image: a function of (P.train_seed, epoch, the item's place in the epoch's list = mini-batch start +
+            # position in it, role 0 / 1 / 2) -- the same on every rank, whatever slice of the mini-batch it builds
+            pos = [item[4] for item in batch]
+            nb = len(batch)
+            ims = [item[2][0] for item in batch] + [item[2][1] for item in batch] + [train_set[item[3]][0] for item in batch]
+            keys = np.concatenate([augment_keys(P.train_seed, epoch, pos, role) for role in range(3)])
+            x = stage_images(ims, P.cuda_device, augment=(aug, keys, P.train_seed))        # the three branches' images: ONE call
+            a, p, ng = x[:nb], x[nb:2 * nb], x[2 * nb:]
+            ids = label_index(labels)
+            lab_ids = torch.tensor([ids[item[0]] for item in batch], dtype=torch.int64)
+            return [a, p, ng], [move_device(lab_ids, P.cuda_device)]
         prep = (lambda im: im) if trans is None else trans
         a = stage_images([prep(im1) for _, _, (im1, _), _ in batch], P.cuda_device)
         p = stage_images([prep(im2) for _, _, (_, im2), _ in batch], P.cuda_device)

@@ -3,6 +3,7 @@ train/siamese_regions.py:26-41), get_siamese_net (:157-168) and the triplet trai
 (train_siam_triplets_pos_couples :45-154): triplet loss on the three region descriptors plus a
 classification loss over the anchor's k selected windows, one triplet per micro-batch (the windows
 differ per image), negatives mined for the whole epoch in one `isx_mine_negatives` launch."""
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -48,7 +49,13 @@ def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, cr
     """one_shape: every training image has the same shape (decided once, in main): create_batch then builds all the items it is given as
     three stacks, which is what lets the training step compute the frozen trunk prefix of a whole mini-batch in one launch and run the rest on
     isx/region_head.py; a set of mixed shapes keeps building one triplet per call."""
+    from ._common import augment_keys, is_augmenter
     trans = None if P.train_pre_proc else P.train_trans
+    aug = trans if is_augmenter(trans) else None        # the reference's random_affine_noisy_cv: one kernel call per batch, not a host callable per image
+    if aug is not None and not one_shape:
+        raise ValueError('train.siamese_regions: the augmenter needs training images of one shape (raw (H,W,3) uint8)')
+    if aug is not None:
+        make_resident(train_set, P.cuda_device)          # the warp reads the resident uint8 rows
     couples = get_pos_couples(train_set)
     log(P, '#pos (without order, with duplicates):{0}'.format(sum(len(c) for c in couples.values())))
 
@@ -57,9 +64,22 @@ def train_siam_triplets_pos_couples(net, train_set, testset_tuple, criterion, cr
         shuffled = shuffle_couples(couples)
         negs = mine_epoch_negatives(similarities, testset_tuple[1], shuffled, epoch < P.train_epoch_switch).tolist()
         negs = [k if k >= 0 else choose_rand_neg_index(train_set, c[0]) for c, k in zip(shuffled, negs)]     # fixed per epoch, on every rank alike
-        return [c + (k,) for c, k in zip(shuffled, negs)], {'epoch': epoch}
+        tagged = [c + (k,) for c, k in zip(shuffled, negs)]
+        if aug is not None:
+            tagged = [c + (i,) for i, c in enumerate(tagged)]       # the item's place in the epoch: what its images' augmentation is keyed on
+        return tagged, {'epoch': epoch}
 
     def create_batch(batch, n, epoch):
+        if aug is not None:
+            # parameters and noise of an image: a function of (P.train_seed, epoch, the item's place in the epoch's list, role 0 / 1 / 2)
+            pos = [item[4] for item in batch]
+            nb = len(batch)
+            ims = [item[2][0] for item in batch] + [item[2][1] for item in batch] + [train_set[item[3]][0] for item in batch]
+            keys = np.concatenate([augment_keys(P.train_seed, epoch, pos, role) for role in range(3)])
+            x = stage_images(ims, P.cuda_device, augment=(aug, keys, P.train_seed))        # the three branches' images: ONE call
+            a, p, ng = x[:nb], x[nb:2 * nb], x[2 * nb:]
+            ids = label_index(labels)
+            return [a, p, ng], [move_device(torch.tensor([ids[item[0]] for item in batch], dtype=torch.int64), P.cuda_device)]
         # one triplet at a time (reference :95-137): the selected windows differ per image.  A set of one image shape: all the items given,
         # three (n, 3, H, W) stacks and (n,) labels -- the micro-batches of the generic route still come one triplet per call
         prep = (lambda im: im) if trans is None else trans
