@@ -52,7 +52,12 @@ int run_topk_chunks(const TopkJob& j) {
     // largest chunk width (multiple of 128 unless it covers N) whose flags + scores fit
     int64_t nc = (int64_t)((j.ws_bytes - fixed_b) / ((size_t)M * 4));
     if (nc > N) nc = N;
-    while (nc > min_nc && topk_chunk_bytes(M, nc) > j.ws_bytes - fixed_b) nc -= (nc > 4096 ? 1024 : 128);
+    // (never below min_nc, which the check above has shown to fit: a workspace a few bytes above the minimum starts at nc = 128 + a few and
+    // used to step down to chunks of those few columns)
+    while (nc > min_nc && topk_chunk_bytes(M, nc) > j.ws_bytes - fixed_b) {
+        nc -= (nc > 4096 ? 1024 : 128);
+        if (nc < min_nc) nc = min_nc;
+    }
     if (nc < N) nc = nc >= 128 ? nc / 128 * 128 : nc;
     if (nc < N && nc >= 4096) {
         // a chunk launch runs ceil(tiles / slots) lock-step rounds of tiles (fp32: 128x128, 512 resident at the

@@ -1,4 +1,5 @@
-"""Guarded device buffers for the tests that call the C ABI directly (test_gpu_trunk_guards.py, test_gpu_retrieval_guards.py).
+"""Guarded device buffers for the tests that call the C ABI directly (test_gpu_trunk_guards.py, test_gpu_retrieval_guards.py,
+test_gpu_fast_guards.py).
 
 A Region is ONE allocation: a leading guard, the body, a trailing guard.  The guards hold a sentinel bit pattern and are compared bit for bit
 after every launch; an OUTPUT body starts as a poison pattern (a NaN with a payload no kernel produces, or an integer no kernel produces) and
@@ -18,6 +19,9 @@ GUARD_I64 = -12345
 POISON_F64 = 0x7FF8DEAD0000DEAD              # a quiet NaN with a payload, as int64 bits
 GUARD_U8 = 0xA5
 POISON_U8 = 0xCD
+POISON_F16 = 0x7EAD                          # a quiet half NaN with a payload (a conversion of a NaN gives 0x7E00 | top payload bits of the source)
+GUARD_OUT_F16 = 0xF1E2                       # -12048.0 as a half
+GUARD_IN_F16 = 0x7EEF                        # half NaN around the fp16 operands
 
 _KIND = {  # kind -> (storage dtype, view dtype, guard, poison)
     "f32": (torch.int32, torch.float32, GUARD_OUT_F32, POISON_F32),
@@ -25,11 +29,12 @@ _KIND = {  # kind -> (storage dtype, view dtype, guard, poison)
     "i64": (torch.int64, torch.int64, GUARD_I64, POISON_I64),
     "f64": (torch.int64, torch.float64, GUARD_I64, POISON_F64),
     "u8": (torch.uint8, torch.uint8, GUARD_U8, POISON_U8),
+    "f16": (torch.int16, torch.float16, GUARD_OUT_F16, POISON_F16),
 }
 
 
 def _signed(v, dtype):
-    bits = {torch.int32: 32, torch.int64: 64}.get(dtype)
+    bits = {torch.int16: 16, torch.int32: 32, torch.int64: 64}.get(dtype)
     return v - (1 << bits) if bits and v >= 1 << (bits - 1) else v
 
 
@@ -52,7 +57,7 @@ class Region:
         else:
             a = np.ascontiguousarray(data)
             assert a.size == self.n and a.dtype.itemsize == item, (a.shape, a.dtype, self.shape)
-            body.copy_(torch.from_numpy(a.reshape(-1).view({1: np.uint8, 4: np.int32, 8: np.int64}[item])))
+            body.copy_(torch.from_numpy(a.reshape(-1).view({1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}[item])))
         self.ptr = self.buf.data_ptr() + self.start * item
         assert self.ptr % item == 0 and (offset or self.ptr % 256 == 0)
 
@@ -86,6 +91,17 @@ def out_i64(shape, guard, offset=0):
 
 def out_f64(shape, guard, offset=0):
     return Region("f64", shape, guard, offset)
+
+
+def out_f16(shape, guard, offset=0):
+    """An fp16 output (int16 storage): poisoned with a half NaN no conversion produces, between sentinel guards."""
+    return Region("f16", shape, guard, offset)
+
+
+def in_f16(a, guard, offset=0):
+    """An fp16 operand between half-NaN guards.  offset counts halfs: the fp16 GEMM needs 16-byte aligned operands (offset % 8 == 0)."""
+    a = np.ascontiguousarray(a, np.float16)
+    return Region("f16", a.shape, guard, offset, data=a, guard_value=GUARD_IN_F16)
 
 
 def in_f32(a, guard=1024, offset=0):
@@ -132,9 +148,9 @@ def assert_clean(outs, ins=(), what=""):
 
 
 def bits(a):
-    """Host array -> its unsigned bit pattern (fp32 -> uint32, fp64 -> uint64)."""
+    """Host array -> its unsigned bit pattern (fp16 -> uint16, fp32 -> uint32, fp64 -> uint64)."""
     a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+    return a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def assert_bits(got, want, what=""):
@@ -170,3 +186,85 @@ def pos_major_rows(B, H, W, Cin, Ho, Wo, Cout, tiles_n64):
 def stream_applicable(M, Cin, Cout, x_ptr):
     """conv1x1_stream_applicable"""
     return Cin == 64 and Cout in (64, 256) and M >= 16384 and x_ptr % 16 == 0
+
+
+# ---- host arithmetic of the fp16 search (csrc/fast.hip, csrc/cosine.hip), restated for tests/test_gpu_fast_guards.py ---------------------------
+HBK = 64                                      # csrc/fast.hip:164  constexpr int HBK = 64  (halfs per k-tile)
+GBM = GBN = 256                               # csrc/fast.hip:290  constexpr int GBM = 256, GBN = 256
+F16_GEMMS = ("cosine_gemm_f16_kernel<false>", "cosine_gemm_f16_kernel<true>",
+             "cosine_gemm_f16_big_kernel<false,false>", "cosine_gemm_f16_big_kernel<false,true>",
+             "cosine_gemm_f16_big_kernel<true,false>", "cosine_gemm_f16_big_kernel<true,true>",
+             "gemm_f16_pp_kernel<false>", "gemm_f16_pp_kernel<true>")     # <FILTER> / <FILTER,FULLK>: the eight instantiations of csrc/fast.hip
+
+
+def f16_gemm_kernel(tile, M, N, D, filt):
+    """launch_gemm_f16 (csrc/fast.hip:671-698): the instantiation ONE launch of M x N x D runs under isx_debug_set_f16_tile(tile);
+    filt = the launch has group flags (a filtered chunk of the search).  None: an empty launch."""
+    if M == 0 or N == 0:
+        return None
+    btm, btn = (M + GBM - 1) // GBM, (N + GBN - 1) // GBN
+    big = tile >= 1 if tile >= 0 else btm * btn >= 512                        # :679
+    f = "true" if filt else "false"
+    if not big:
+        return "cosine_gemm_f16_kernel<%s>" % f                                # :694-695
+    fullk = D % HBK == 0                                                      # :682
+    if fullk and tile != 2:                                                   # :683-685
+        return "gemm_f16_pp_kernel<%s>" % f
+    return "cosine_gemm_f16_big_kernel<%s,%s>" % (f, "true" if fullk else "false")    # :686-689
+
+
+def a256(v):
+    return (v + 255) // 256 * 256
+
+
+def topk_fixed_bytes(M, k):
+    """csrc/cosine.hip:26"""
+    return a256(M * k * 8) + a256(M * 4)
+
+
+def topk_chunk_bytes(M, nc):
+    """csrc/cosine.hip:27"""
+    return a256(M * ((nc + 31) // 32)) + M * nc * 4
+
+
+def fast_kl(k):
+    """csrc/fast.hip:857-863: candidates kept per query by the approximate pass."""
+    return min(max((200 * k // 100 + 32 + 31) // 32 * 32, 64), 256)
+
+
+def topk_chunks(M, N, k, avail, f16):
+    """run_topk_chunks (csrc/cosine.hip:41-116) for k <= 256: the column chunks [(c0, width, filtered)] of a search whose workspace holds `avail`
+    bytes (everything of the job's workspace, the fixed part included).  The first chunk is always plain (and short only from N = 32768 on),
+    every later one runs the filter epilogue with ngrp = ceil(width / 32)."""
+    assert k <= 256
+    fixed, min_nc = topk_fixed_bytes(M, k), min(N, 128)
+    assert avail >= fixed + topk_chunk_bytes(M, min_nc)
+    nc = min((avail - fixed) // (M * 4), N)
+    while nc > min_nc and topk_chunk_bytes(M, nc) > avail - fixed:
+        nc = max(nc - (1024 if nc > 4096 else 128), min_nc)
+    if nc < N and nc >= 128:
+        nc = nc // 128 * 128
+    if nc < N and nc >= 4096:
+        tile, slots = (256, 256) if f16 else (128, 512)
+        tm, tn, tries = (M + tile - 1) // tile, nc // tile, 0
+        while tries < 16 and tn > 16:
+            rem = tm * tn % slots
+            if rem == 0 or rem >= slots * 9 // 10:
+                nc = tn * tile
+                break
+            tn, tries = tn - 1, tries + 1
+    out, c0 = [], 0
+    while c0 < N:
+        w = min(N - c0, nc)
+        if c0 == 0 and w > 8192 and N >= 4 * 8192:
+            w = 8192
+        out.append((c0, w, c0 != 0))
+        c0 += w
+    return out
+
+
+def fast_layout(M, N, D, k, own_gallery):
+    """fast_layout (csrc/fast.hip:866-891): (offset of the chunk area shared by the two pipelines, bytes of isx_cosine_topk_fast_workspace)."""
+    o = a256(M * D * 2) + a256(M * 4) + 256 + (a256(N * D * 2) if own_gallery else 0) + 256 + 2 * a256(M * 4) + 256 + a256(M * D * 4)
+    nc = N if M * N * 4 <= 1 << 30 else min(max((1 << 30) // (M * 4) // 2048 * 2048, 2048), N)
+    return o, o + topk_fixed_bytes(M, fast_kl(k)) + topk_chunk_bytes(M, nc)
