@@ -221,6 +221,12 @@ int isx_boxpool_s1_nhwc(const float* fmap, int64_t B, int C, int H, int W, int k
 
 /* ---- region path ----------------------------------------------------------- */
 
+/* NaN class scores, one rule for the four class-max entry points below (both layouts) and the oracle: a location with a NaN score in ANY
+ * class has the canonical quiet NaN 0x7FC00000 as its class-max, whatever the sign or payload of the input -- the reference's c.max(1)
+ * propagates a NaN from any class.  Such a location ranks FIRST (above +inf, as torch.topk ranks a NaN); ties among such locations are
+ * broken like any other tie (isx_region_topk: the lowest flat index; isx_best_location_desc: the lowest column, then the lowest row), and the
+ * score isx_region_topk emits for it is that NaN.  Inputs without a NaN are not affected by the rule. */
+
 /* train/classif_regions.py:118-128: class-max map, spatial arg-max (smallest column,
  * then smallest row on ties), gather the K class scores there, L2.
  * cls: (B,K,Hp,Wp); desc: (B,K); loc: (B,2) = {row i1, col i2}.  -0 and +0 are one score.  Sum of squares: thread t of 256 adds classes
@@ -230,7 +236,8 @@ int isx_best_location_desc(const float* cls, int64_t B, int K, int Hp, int Wp, f
 
 /* model/siamese.py:191-194: c_maxv = c.max(1).view(-1); topk(min(len,k)) in canonical
  * order, for every image of a batch (the reference walks one image per call, :184).
- * cls: (B,K,Hp,Wp); flat_idx, score: (B,k); entries past Hp*Wp are (-1, -inf).  Hp*Wp <= 4096. */
+ * cls: (B,K,Hp,Wp); flat_idx, score: (B,k); entries past Hp*Wp are (-1, -inf).  Hp*Wp <= 4096.  -0 and +0 are one score, emitted as +0;
+ * a location with a NaN class score ranks first and is emitted with the score 0x7FC00000 (the NaN rule above). */
 int isx_region_topk(const float* cls, int64_t B, int K, int Hp, int Wp, int k, int64_t* flat_idx, float* score,
                     isx_stream_t stream);
 

@@ -15,6 +15,11 @@ __device__ __forceinline__ uint64_t loc_key(float v, int row, int col, int Hp) {
     return ((uint64_t)f32_orderable(v) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(col * Hp + row));
 }
 
+// NaN rule of the class-max (include/isx.h): a location with a NaN score in ANY class has the canonical quiet NaN as its maximum, whatever the
+// sign or payload of the input (the reference's c.max(1) propagates a NaN from any class).  Its orderable image 0xFFC00000 lies above +inf's: such
+// a location ranks first (as torch.topk ranks a NaN), ties among them by the index like any other tie.
+__device__ __forceinline__ float class_max_nan() { return __uint_as_float(0x7FC00000u); }
+
 // One 256-thread block per image.
 __global__ __launch_bounds__(256) void best_location_desc_kernel(const float* __restrict__ cls, int K, int Hp, int Wp,
                                                                  float eps, float* __restrict__ desc,
@@ -26,7 +31,9 @@ __global__ __launch_bounds__(256) void best_location_desc_kernel(const float* __
     uint64_t best = 0;
     for (int p = threadIdx.x; p < P; p += 256) {
         float m = c[p];
-        for (int k = 1; k < K; ++k) { float v = c[(int64_t)k * P + p]; m = v > m ? v : m; }
+        bool nan = m != m;
+        for (int k = 1; k < K; ++k) { float v = c[(int64_t)k * P + p]; m = v > m ? v : m; nan |= v != v; }
+        if (nan) m = class_max_nan();
         uint64_t key = loc_key(m, p / Wp, p % Wp, Hp);
         best = key > best ? key : best;
     }
@@ -58,7 +65,9 @@ __global__ __launch_bounds__(256) void region_topk_kernel(const float* __restric
         uint64_t key = 0;
         if (p < P) {
             float m = cls[p];
-            for (int c = 1; c < K; ++c) { float v = cls[(int64_t)c * P + p]; m = v > m ? v : m; }
+            bool nan = m != m;
+            for (int c = 1; c < K; ++c) { float v = cls[(int64_t)c * P + p]; m = v > m ? v : m; nan |= v != v; }
+            if (nan) m = class_max_nan();
             key = rank_key(m, (uint32_t)p);
         }
         keys[p] = key;
@@ -108,9 +117,11 @@ __global__ __launch_bounds__(1024) void region_gather_l2_kernel(const float* __r
 // class-max of location p by one wave: lanes stride the K contiguous scores
 __device__ __forceinline__ float wave_class_max(const float* __restrict__ row, int K, int lane) {
     float m = -INFINITY;
-    for (int k = lane; k < K; k += 64) { const float v = row[k]; m = v > m ? v : m; }
+    bool nan = false;
+    for (int k = lane; k < K; k += 64) { const float v = row[k]; m = v > m ? v : m; nan |= v != v; }
+    if (nan) m = class_max_nan();
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float w = __shfl_xor(m, o, 64); m = w > m ? w : m; }
+    for (int o = 32; o > 0; o >>= 1) { const float w = __shfl_xor(m, o, 64); m = (w > m || w != w) ? w : m; }   // a lane's NaN reaches every lane
     return m;
 }
 

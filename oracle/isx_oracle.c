@@ -118,8 +118,21 @@ ISXO_API void isxo_boxpool_s1(const float* fmap, int64_t B, int C, int H, int W,
 
 /* ------------------------------------------------------- region path ------ */
 
+/* Class-max of location p of a (K, P) score map, model/siamese.py:191 c.max(1): the first largest score; a NaN in ANY class makes the
+ * maximum the canonical quiet NaN 0x7FC00000 whatever its sign or payload (torch's max propagates a NaN from any class). */
+static float class_max(const float* cls, int K, int P, int p) {
+    float m = cls[p];
+    int nan = m != m;
+    for (int c = 1; c < K; ++c) { float v = cls[(size_t)c * P + p]; if (v > m) m = v; if (v != v) nan = 1; }
+    if (nan) { const uint32_t q = 0x7FC00000u; memcpy(&m, &q, 4); }
+    return m;
+}
+
+/* a ranks above b: a NaN maximum ranks above every number (as torch.topk and max rank it), NaNs tie among themselves */
+static int score_above(float a, float b) { return a != a ? b == b : a > b; }
+
 /* train/classif_regions.py:118-128:
- *   max_pred = out.max(1)            (max over classes)      -> (1,1,H',W')
+ *   max_pred = out.max(1)           (max over classes)      -> (1,1,H',W')
  *   max_pred1, max_i1 = max_pred.max(2)  (over rows, per column)
  *   _, max_i2 = max_pred1.max(3)     (over columns)
  *   i2 = max_i2[0]; i1 = max_i1[i2];  desc = NormalizeL2(out[:, :, i1, i2])
@@ -128,16 +141,12 @@ ISXO_API void isxo_boxpool_s1(const float* fmap, int64_t B, int C, int H, int W,
 ISXO_API void isxo_best_location_desc(const float* cls, int K, int Hp, int Wp, float eps, float* desc, int64_t* loc) {
     const int P = Hp * Wp;
     float* mx = (float*)malloc(sizeof(float) * (size_t)P);
-    for (int p = 0; p < P; ++p) {
-        float m = cls[p];
-        for (int c = 1; c < K; ++c) { float v = cls[(size_t)c * P + p]; if (v > m) m = v; }
-        mx[p] = m;
-    }
+    for (int p = 0; p < P; ++p) mx[p] = class_max(cls, K, P, p);
     int bi2 = 0, bi1 = 0; float best = 0.0f;
     for (int j = 0; j < Wp; ++j) {
         int i1 = 0; float cm = mx[j];
-        for (int i = 1; i < Hp; ++i) if (mx[i * Wp + j] > cm) { cm = mx[i * Wp + j]; i1 = i; }
-        if (j == 0 || cm > best) { best = cm; bi2 = j; bi1 = i1; }
+        for (int i = 1; i < Hp; ++i) if (score_above(mx[i * Wp + j], cm)) { cm = mx[i * Wp + j]; i1 = i; }
+        if (j == 0 || score_above(cm, best)) { best = cm; bi2 = j; bi1 = i1; }
     }
     float* v = (float*)malloc(sizeof(float) * (size_t)K);
     for (int c = 0; c < K; ++c) v[c] = cls[(size_t)c * P + bi1 * Wp + bi2];
@@ -154,8 +163,8 @@ ISXO_API int isxo_region_topk(const float* cls, int K, int Hp, int Wp, int k, in
     kv_t* kv = (kv_t*)malloc(sizeof(kv_t) * (size_t)P);
     float* mx = (float*)malloc(sizeof(float) * (size_t)P);
     for (int p = 0; p < P; ++p) {
-        float m = cls[p];
-        for (int c = 1; c < K; ++c) { float v = cls[(size_t)c * P + p]; if (v > m) m = v; }
+        float m = class_max(cls, K, P, p);
+        if (m == 0.0f) m = 0.0f;                 /* -0 and +0 are one score, emitted as +0 (what the ranking key holds) */
         mx[p] = m; kv[p].key = rank_key(m, (uint64_t)p);
     }
     qsort(kv, (size_t)P, sizeof(kv_t), cmp_key_desc);

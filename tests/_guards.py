@@ -1,5 +1,5 @@
 """Guarded device buffers for the tests that call the C ABI directly (test_gpu_trunk_guards.py, test_gpu_retrieval_guards.py,
-test_gpu_fast_guards.py).
+test_gpu_fast_guards.py, test_gpu_eval_guards.py).
 
 A Region is ONE allocation: a leading guard, the body, a trailing guard.  The guards hold a sentinel bit pattern and are compared bit for bit
 after every launch; an OUTPUT body starts as a poison pattern (a NaN with a payload no kernel produces, or an integer no kernel produces) and

@@ -17,20 +17,7 @@ pytestmark = pytest.mark.gpu
 
 
 # ---- isx_boxpool_s1_bwd_nhwc ------------------------------------------------------------------------------------------------------------------
-def _canonical_boxpool_bwd(g, H, W, kh, kw):
-    """g: (B, Ho, Wo, C) float32 numpy.  dx[b,i,j,c] = (sum over the windows covering (i, j): rows p ascending outside, columns q ascending
-    inside, fp32 adds from +0) / (kh kw), one IEEE division."""
-    B, Ho, Wo, C = g.shape
-    dx = np.empty((B, H, W, C), dtype=np.float32)
-    div = np.float32(kh * kw)
-    for i in range(H):
-        for j in range(W):
-            s = np.zeros((B, C), dtype=np.float32)
-            for p in range(max(0, i - kh + 1), min(Ho - 1, i) + 1):
-                for q in range(max(0, j - kw + 1), min(Wo - 1, j) + 1):
-                    s = s + g[:, p, q, :]
-            dx[:, i, j, :] = s / div
-    return dx
+from _eval_model import boxpool_bwd_canonical as _canonical_boxpool_bwd
 
 
 @pytest.mark.parametrize("B,H,W,kh,kw,C", [(2, 14, 14, 7, 7, 64), (1, 9, 11, 3, 5, 8), (3, 7, 7, 7, 7, 2048), (2, 6, 6, 1, 1, 4), (1, 10, 10, 7, 7, 260)])

@@ -333,8 +333,8 @@ def test_rank_full_and_ap(ops, M, N):
 @pytest.mark.parametrize("M,N,L", [(12, 40, 6), (9, 1000, 100), (5, 5000, 50), (4, 3000, 3), (20, 10000, 1000), (7, 40001, 50), (12, 100000, 5000), (3, 16384, 600), (6, 32768, 40), (5, 65536, 8192), (4, 65537, 6000), (9, 10000, 2000), (5, 40000, 200), (3, 33001, 150), (4, 2048, 8), (3, 6000, 3), (4, 20480, 20), (2, 100000, 110)])
 def test_average_precision_sim_equals_sorted_path(ops, M, N, L):
     """Sort-free AP == rank_full + average_precision == oracle, bit for bit (incl. kth > 1, skipped
-    queries, tied scores, rows with up to 1024 positives counted in chunks of 32 -- 1000, 1024, 909 per query among the cases -- and rows with
-    more (2000) that take the sorted fallback)."""
+    queries, tied scores, and rows with 909, 1000, 1024 and 2000 positives, all below the 2048 the sort-free kernel ranks in LDS; the rows at
+    and above that limit -- 2048 positives, and 2049, which take the sorted fallback -- are in tests/test_gpu_eval_guards.py)."""
     rng = np.random.default_rng(N + L)
     sim = (np.round(rng.random((M, N)) * 200) / 200).astype(np.float32)        # many exact ties
     gl = (np.arange(N) % L).astype(np.int32)
