@@ -184,7 +184,10 @@ class FlatGrads(object):
 
 class TreeExchange(object):
     """Sum of every rank's flat buffer in the canonical tree order, result on every rank.  all-to-all (slice j -> rank j) + tree-ordered
-    sum of the P pieces + all-gather of the reduced slices; point-to-point friendly (each pair of GPUs exchanges 2 x n/P floats)."""
+    sum of the P pieces + all-gather of the reduced slices; point-to-point friendly (each pair of GPUs exchanges 2 x n/P floats).
+    An exchange object belongs to ONE stream: its padded staging buffer is reused by every allreduce_ and nothing orders two streams on it
+    (the training step calls it from the stream it runs on; the collectives inside order the ranks, not the streams).  The stream is the
+    one that is current at the first allreduce_ of a device buffer; a call under another current stream is refused (IsxError)."""
 
     def __init__(self, group=None):
         self.group = group
@@ -193,8 +196,16 @@ class TreeExchange(object):
         if not is_power_of_two(self.world):
             raise ValueError("TreeExchange needs a power-of-two world size")
         self._pad = None
+        self._stream = {}                     # device -> stream handle of the first call with a buffer of that device
 
     def allreduce_(self, flat):
+        if flat.is_cuda:
+            here = torch.cuda.current_stream(flat.device).cuda_stream
+            first = self._stream.setdefault(flat.device, here)
+            if first != here:
+                from ._lib import IsxError
+                raise IsxError("TreeExchange: this exchange belongs to stream %#x of %s, called under stream %#x -- one exchange object per "
+                               "stream (its staging buffer is not ordered across streams)" % (first, flat.device, here))
         P = self.world
         if P == 1 or flat.numel() == 0:
             return flat

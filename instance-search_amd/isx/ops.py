@@ -146,9 +146,6 @@ def l2norm_shift_rows(x, shift=None, eps=EPS):
     return y
 
 
-_HEAD_WS = {}
-
-
 def head_linear_applicable(rows, weight, any_width=False):
     """any_width: N need not be a multiple of 64 nor K of 32 (head_linear_any pads the weight with zeros)."""
     K = weight.size(1) if weight.dim() == 2 else 0
@@ -206,11 +203,9 @@ def head_linear(rows, weight, bias=None):
     y = torch.empty((M, N), dtype=torch.float32, device=dev)
     if M == 0:
         return y
-    need = lib().isx_head_linear_rows_workspace(M, K, N) // 4
-    key = rows.device.index
-    ws = _HEAD_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _HEAD_WS[key] = torch.empty(need, dtype=torch.float32, device=rows.device)
+    # the split-K workspace is a fresh allocation per call: the caching allocator keeps a stream's blocks to that stream, so two calls under
+    # two current streams never share scratch memory (a workspace cached per device did)
+    ws = torch.empty(lib().isx_head_linear_rows_workspace(M, K, N) // 4, dtype=torch.float32, device=dev)
     _launch("isx_head_linear_fwd_rows", rows.data_ptr(), M, K, weight.data_ptr(), N, _ptr(bias), y.data_ptr(), ws.data_ptr(), ws.numel() * 4)
     return y
 
@@ -260,15 +255,26 @@ _MEAN_STD = {}
 
 
 def _mean_std_device(mean, std, device):
-    """(6,) fp32 device tensor mean | std, cached per (values, device): the kernel reads them from device memory."""
+    """(6,) fp32 device tensor mean | std, cached per (values, device) for the life of the process (a constant is never dropped: a launch on
+    some stream may still be reading it): the kernel reads them from device memory.  The constant is copied
+    asynchronously from a pinned block on the stream that is current when it is first asked for (the host does not wait); a caller under ANOTHER
+    stream is ordered behind that copy with an event wait until the copy has completed."""
     key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), device)
-    t = _MEAN_STD.get(key)
-    if t is None:
+    entry = _MEAN_STD.get(key)
+    stream = torch.cuda.current_stream(device)
+    if entry is None:
         if len(key[0]) != 3 or len(key[1]) != 3 or 0.0 in key[1]:
             raise _lib.IsxError("mean and std must be three values each, std non-zero")
-        _MEAN_STD.clear()
-        t = _MEAN_STD[key] = torch.tensor(key[0] + key[1], dtype=torch.float32, device=device)
-    return t
+        t = torch.tensor(key[0] + key[1], dtype=torch.float32).pin_memory().to(device, non_blocking=True)
+        created = torch.cuda.Event()
+        created.record(stream)
+        entry = _MEAN_STD[key] = [t, created, stream.cuda_stream]
+    elif entry[1] is not None:
+        if entry[1].query():
+            entry[1] = None                     # visible to every stream from now on
+        elif entry[2] != stream.cuda_stream:
+            stream.wait_event(entry[1])
+    return entry[0]
 
 
 def affine_noisy(img_u8, rows, mats, seed, noise_ids, mean, std, channels_last=True, want_u8=False):

@@ -188,6 +188,10 @@ class ShardedGallery(object):
         self._fb_host = None
         self._fb_event = None
         self._fb_rows = 0
+        # The workspace, the fp16 image and the fallback counter are shared by every search of this object: searches on ONE stream are in
+        # stream order; a search under another stream than the previous one waits for that one's last launch (an event wait, no host wait).
+        self._stream = None
+        self._done = None
 
     @classmethod
     def from_full(cls, gallery, group=None):
@@ -230,7 +234,13 @@ class ShardedGallery(object):
             self._fb_event = None
 
     def local_search(self, Q, k):
-        """This rank's shard only (no collective): canonical top-k with global indices."""
+        """This rank's shard only (no collective): canonical top-k with global indices.  Enqueued on torch's current stream, behind the previous
+        search of this gallery whatever stream that one ran on."""
+        cur = None
+        if self.shard.is_cuda:
+            cur = torch.cuda.current_stream(self.shard.device)
+            if self._done is not None and self._stream != cur.cuda_stream:
+                cur.wait_event(self._done)
         if self.fast:
             self._check_fallback()
         if self.fast and self._f16 is None and self.shard.size(0) > 0:
@@ -248,6 +258,11 @@ class ShardedGallery(object):
                 self._fb_rows = Q.size(0)
                 self._fb_event = torch.cuda.Event()
                 self._fb_event.record(torch.cuda.current_stream(self.shard.device))
+        if cur is not None:
+            if self._done is None:
+                self._done = torch.cuda.Event()
+            self._done.record(cur)
+            self._stream = cur.cuda_stream
         return out
 
     def average_precisions(self, Q, qlab, glab_local, kth=1, budget_bytes=None):

@@ -143,7 +143,9 @@ _READ_POOL = None
 
 
 def _read_stage(floats):
-    """Two pinned staging buffers of at least `floats` floats (allocated once: pinning 2 x 64 MB costs as much as reading 1 GB)."""
+    """Two pinned staging buffers of at least `floats` floats (allocated once: pinning 2 x 64 MB costs as much as reading 1 GB).  They belong to
+    load_slab, which is called from one host thread at a time and drains the device before it returns: whatever stream the next load runs under,
+    both buffers are free when it starts."""
     if not _STAGE or _STAGE[0].numel() < floats:
         del _STAGE[:]
         _STAGE.extend(torch.empty((floats,), dtype=torch.float32).pin_memory() for _ in range(2))
@@ -188,7 +190,8 @@ def slab_info(path):
 
 def load_slab(path, device="cpu", rows=None):
     """(descriptors (n, D) fp32 tensor on `device`, labels (n,) int32 tensor or None) for the row range
-    `rows` = (lo, hi) (default: all).  GPU loads stream through a pinned staging buffer."""
+    `rows` = (lo, hi) (default: all).  GPU loads stream through a pinned staging buffer on torch's current stream and BLOCK the host: the call
+    returns after torch.cuda.synchronize(device), with the rows in place and the staging buffers free for a load under any other stream."""
     info = slab_info(path)
     N, D = info["rows"], info["dim"]
     lo, hi = (0, N) if rows is None else rows

@@ -62,6 +62,40 @@ def unit(rng, n, d):
     return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(F)
 
 
+# ---- models and bounds shared with tests/test_gpu_stream_order.py ------------------------------------------------------------------------------
+def norm2_within(got, x, what=""):
+    """norm2 of isx_rows_to_f16 is an upper bound of the exact sum of squares that D + 1 fp32 roundings and the kernel's own 1.000001 explain."""
+    D = x.shape[1]
+    exact = (x.astype(np.float64) ** 2).sum(1)
+    got = np.asarray(got).astype(np.float64)
+    assert (got >= exact * (1 - 1e-6)).all(), what
+    assert (got <= exact * (1 + 2e-6 + (D + 2) * 2.0 ** -23)).all(), what
+
+
+def gallery_f16_model(Gm):
+    """(Gh, n2max, amax, lost) of isx_gallery_to_f16: power-of-two scaling into [2^13, 2^14), RNE, results below the fp16 normal range stored
+    as +0; the largest squared norm, max |x| and the largest squared loss of a row."""
+    amax = np.abs(Gm).max()
+    scale = 2.0 ** (13 - np.floor(np.log2(amax)))
+    want = (Gm * F(scale)).astype(H)
+    want[np.abs(want.astype(F)) < 2.0 ** -14] = 0
+    lost = ((Gm.astype(np.float64) - want.astype(np.float64) / scale) ** 2).sum(1).max()
+    return want, (Gm.astype(np.float64) ** 2).sum(1).max(), amax, lost
+
+
+def gstats_within(s, n2max, amax, lost, D, what=""):
+    """gstats = {max squared norm (upper bound), max |x|, largest squared loss of a row (upper bound within 0.1 %), 0}."""
+    assert s[1] == amax and s[3] == 0.0 and G.bits(s)[3] == 0, (what, s.tolist())
+    assert n2max * (1 - 1e-6) <= s[0] <= n2max * (1 + 2e-6 + (D + 2) * 2.0 ** -23), (what, s.tolist(), n2max)
+    assert lost <= s[2] <= lost * 1.001, (what, s.tolist(), lost)
+
+
+def sim_f16_bound(q, g):
+    """(float64 product, bound) of isx_cosine_sim_f16: fp16 products are exact in fp32, only the D accumulation steps round."""
+    q64, g64 = q.astype(np.float64), g.astype(np.float64)
+    return q64 @ g64.T, (np.abs(q64) @ np.abs(g64).T) * q.shape[1] * 2.0 ** -23 + 1e-30
+
+
 # ---- 1. isx_rows_to_f16, isx_gallery_to_f16 --------------------------------------------------------------------------------------------------------
 CONV_SHAPES = [(B, D) for B in (1, 5, 67) for D in (8, 200, 2056)]      # B = 5: a last block of one row; D = 200 / 2056: lanes idle / a fourth pass of lane 0
 
@@ -78,7 +112,6 @@ def test_rows_to_f16(B, D):
     x[0, :min(D, 50)] = rng.standard_normal(min(D, 50)).astype(F) * F(1e-6)          # fp16 subnormal range
     x[min(1, B - 1), :8] = [65504.0, -65504.0, 6.1e-5, 5.96e-8, 2.9e-8, 0.0, -0.0, 1.0009765625]
     want_h = x.astype(H)
-    exact = (x.astype(np.float64) ** 2).sum(1)
     for ox, oh in ((0, 0), (1, 0), (0, 1), (1, 1)):
         what = ("offsets", ox, oh)
         gx = G.in_f32(x, 8 * D + 1024, ox)
@@ -88,9 +121,7 @@ def test_rows_to_f16(B, D):
         G.assert_clean([h, n2, am], [gx], what)
         G.assert_bits(h, want_h, what)
         G.assert_bits(am, np.abs(x).max(1), what)
-        got = n2.host().astype(np.float64)
-        assert (got >= exact * (1 - 1e-6)).all(), what
-        assert (got <= exact * (1 + 2e-6 + (D + 2) * 2.0 ** -23)).all(), what
+        norm2_within(n2.host(), x, what)
 
 
 @gpu
@@ -105,13 +136,8 @@ def test_gallery_to_f16(N, D):
     r = min(3, N - 1)
     Gm[r, 1:6] = F(1e-12) * np.arange(1, 6, dtype=F)                                  # below the fp16 normal range after scaling
     Gm[r, 6] = F(-1e-12)                                                              # and a negative one: flushed to +0
-    amax = np.abs(Gm).max()
-    scale = 2.0 ** (13 - np.floor(np.log2(amax)))
-    want = (Gm * F(scale)).astype(H)
-    want[np.abs(want.astype(F)) < 2.0 ** -14] = 0
+    want, n2max, amax, lost = gallery_f16_model(Gm)
     assert (want[r, 1:7].view(np.uint16) == 0).all()
-    lost = ((Gm.astype(np.float64) - want.astype(np.float64) / scale) ** 2).sum(1).max()
-    n2max = (Gm.astype(np.float64) ** 2).sum(1).max()
     assert lost > 0
     for ox in (0, 1):
         gx = G.in_f32(Gm, 8 * D + 1024, ox)
@@ -121,10 +147,7 @@ def test_gallery_to_f16(N, D):
             _ok(L.isx_gallery_to_f16(gx.ptr, N, D, gh.ptr, gs.ptr, st), ox)
         G.assert_clean([gh, gs], [gx], ox)
         G.assert_bits(gh, want, ox)
-        s = gs.host()
-        assert s[1] == amax and s[3] == 0.0 and G.bits(s)[3] == 0, (ox, s.tolist())
-        assert n2max * (1 - 1e-6) <= s[0] <= n2max * (1 + 2e-6 + (D + 2) * 2.0 ** -23), (ox, s.tolist(), n2max)
-        assert lost <= s[2] <= lost * 1.001, (ox, s.tolist(), lost)
+        gstats_within(gs.host(), n2max, amax, lost, D, ox)
 
 
 @gpu
@@ -185,9 +208,7 @@ def test_cosine_sim_f16(case):
     g = rng.standard_normal((N, D)).astype(H)
     q[0] = (rng.standard_normal(D) * 3e-6).astype(H)                          # subnormal halves
     g[0] = (rng.standard_normal(D) * 3e-6).astype(H)
-    q64, g64 = q.astype(np.float64), g.astype(np.float64)
-    want = q64 @ g64.T
-    bound = (np.abs(q64) @ np.abs(g64).T) * D * 2.0 ** -23 + 1e-30
+    want, bound = sim_f16_bound(q, g)
     ins = [G.in_f16(q, 256 * D), G.in_f16(g, 256 * D)]
     assert (ins[0].ptr | ins[1].ptr) % 16 == 0
     first = None
@@ -353,19 +374,25 @@ def test_cosine_topk_fast(case, cached):
 FALLBACK_SHAPE = (9, 1024, 64, 20)
 
 
-@gpu
-@pytest.mark.parametrize("cached", [True, False])
-def test_fallback_rows_write_through_the_row_map(cached):
-    L, st = _lib()
+def fallback_case():
+    """(Q, G) of FALLBACK_SHAPE: 8 centres, 1e-4 perturbations, two duplicates of row 3."""
     M, N, D, k = FALLBACK_SHAPE
-    assert G.f16_gemm_kernel(1, M, N, D, False) == PP
     rng = np.random.default_rng(7)
     c = unit(rng, 8, D)
     Gm = c[rng.integers(0, 8, N)] + F(1e-4) * rng.standard_normal((N, D), dtype=F)
     Gm = (Gm / np.linalg.norm(Gm, axis=1, keepdims=True)).astype(F)
     Gm[N // 2] = Gm[3]
     Gm[N - 1] = Gm[3]
-    Q = unit(rng, M, D)
+    return unit(rng, M, D), Gm
+
+
+@gpu
+@pytest.mark.parametrize("cached", [True, False])
+def test_fallback_rows_write_through_the_row_map(cached):
+    L, st = _lib()
+    M, N, D, k = FALLBACK_SHAPE
+    assert G.f16_gemm_kernel(1, M, N, D, False) == PP
+    Q, Gm = fallback_case()
     want = O.cosine_topk(Q, Gm, k, idx_base=IDX_BASE)
     regions = _cached_gallery(L, st, Gm, cached)
     for nc in (None, 256):
