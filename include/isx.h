@@ -14,8 +14,16 @@
  *   - every call only ENQUEUES work on `stream` (a hipStream_t passed as void*) and
  *     returns; no allocation, no synchronisation, no global state in the entry points
  *     declared here: safe to capture in a hipGraph and re-entrant from several host
- *     threads on distinct streams (the test hooks at the end of this file are the
- *     exception)
+ *     threads on distinct streams.  tests/test_gpu_graph_capture.py holds this for every
+ *     function below whose last parameter is `isx_stream_t stream`: captured on one stream
+ *     and replayed over the leftovers of earlier replays (kernels only -- nothing is zeroed
+ *     with hipMemsetAsync, whose graph node replays wrongly), and called from four host
+ *     threads at once; tests/test_gpu_stream_order.py holds the stream order.  OUTSIDE the
+ *     contract: the isx_comm_* set-up calls (they allocate and talk to the other ranks) and
+ *     the two collectives isx_comm_allgather_rows / isx_shard_topk_allgather, which are not
+ *     captured by any test; and the debug hooks at the end of this file, which are
+ *     process-global (relaxed atomics, read when a call picks its path: a captured graph
+ *     keeps the path of its capture) and of which isx_debug_fast_fallback_rows blocks the host
  *   - the library reads no environment except the initial values of the test hooks
  *     (ISX_DEBUG_GEMM_CFG, ISX_DEBUG_CONV_CFG; see the end of this file)
  *   - return 0 = ISX_OK, <0 = error; isx_last_error() gives a thread-local message

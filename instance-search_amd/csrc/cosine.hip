@@ -22,6 +22,28 @@ constexpr int64_t kFirstChunk = 8192;
 constexpr size_t kChunkBudget = (size_t)1 << 30;          // score-chunk budget of topk_recommended_chunk: 1 GiB
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// ---- zero fill (isx_internal.hpp: the library's replacement of hipMemsetAsync) --------------------
+template <typename T> __global__ __launch_bounds__(256) void zero_fill_kernel(T* __restrict__ p, size_t n) {
+    T z;
+    __builtin_memset(&z, 0, sizeof(T));
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = z;
+}
+
+int zero_words_async(void* p, size_t bytes, hipStream_t st, const char* who) {
+    if (bytes == 0) return ISX_OK;
+    if (!p || bytes % 4 || (uintptr_t)p % 4) {
+        isx_set_error("%s: zero fill of %zu bytes at a pointer that is null or off a 4-byte boundary", who, bytes);
+        return ISX_ERR_ARG;
+    }
+    const bool wide = (uintptr_t)p % 16 == 0 && bytes % 16 == 0;              // 16-byte stores where the range allows them
+    const size_t n = bytes / (wide ? 16 : 4), blocks = (n + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);          // grid-stride beyond 1 Mi elements
+    if (wide) hipLaunchKernelGGL(zero_fill_kernel<uint4>, dim3(grid), dim3(256), 0, st, (uint4*)p, n);
+    else hipLaunchKernelGGL(zero_fill_kernel<uint32_t>, dim3(grid), dim3(256), 0, st, (uint32_t*)p, n);
+    ISX_CHECK_LAUNCH(who);
+    return ISX_OK;
+}
+
 // ---- chunked running top-k driver (shared by isx_cosine_topk and the fast path of fast.hip) ------
 size_t topk_fixed_bytes(int64_t M, int k) { return align256((size_t)M * k * 8) + align256((size_t)M * 4); }
 size_t topk_chunk_bytes(int64_t M, int64_t nc) { return align256((size_t)M * ((nc + 31) / 32)) + (size_t)M * nc * 4; }
@@ -97,10 +119,8 @@ int run_topk_chunks(const TopkJob& j) {
             // bootstrap chunk: plain GEMM, every group present, empty carry (all-zero keys sort last)
             rc = gemm(c0, w, nullptr, nullptr);
             if (rc) return rc;
-            if (hipMemsetAsync(carry, 0, (size_t)M * k * 8, st) != hipSuccess) {
-                isx_set_error("%s: hipMemsetAsync failed", j.who);
-                return ISX_ERR_HIP;
-            }
+            rc = zero_words_async(carry, (size_t)M * k * 8, st, j.who);
+            if (rc) return rc;
             rc = launch_select_groups(chunk, nullptr /* all groups present */, M, w, w, c0, k, carry, thr, emit ? 1 : (last ? 2 : 0), j.idx_base, j.top_score,
                                       j.top_idx, st, j.m_active, j.row_map, j.win, j.k_win);
         } else {

@@ -924,7 +924,8 @@ static int convert_scaled(const float* x, int64_t B, int D, _Float16* h, float* 
 ISX_API int isx_gallery_to_f16(const float* G, int64_t N, int D, void* Gh, float* gstats, isx_stream_t stream) {
     ISX_REQUIRE(N >= 0 && D > 0 && N < (1ll << 33), "isx_gallery_to_f16: bad shape N=%lld D=%d", (long long)N, D);
     ISX_REQUIRE(gstats && ((G && Gh) || N == 0), "isx_gallery_to_f16: null pointer");
-    if (hipMemsetAsync(gstats, 0, 16, (hipStream_t)stream) != hipSuccess) { isx_set_error("isx_gallery_to_f16: hipMemsetAsync failed"); return ISX_ERR_HIP; }
+    const int zrc = zero_words_async(gstats, 16, (hipStream_t)stream, "isx_gallery_to_f16");
+    if (zrc) return zrc;
     if (N == 0) return ISX_OK;
     return convert_scaled(G, N, D, (_Float16*)Gh, nullptr, nullptr, (unsigned*)gstats, 1, (hipStream_t)stream);
 }
@@ -982,7 +983,8 @@ ISX_API int isx_cosine_topk_fast(const float* Q, int64_t M, const float* G, int6
     int rc;
 
     // 1. fp16 operands
-    if (hipMemsetAsync(qst, 0, 16, st) != hipSuccess) { isx_set_error("isx_cosine_topk_fast: hipMemsetAsync failed"); return ISX_ERR_HIP; }
+    rc = zero_words_async(qst, 16, st, "isx_cosine_topk_fast");
+    if (rc) return rc;
     float* qres2 = (float*)ok;                          // per-row conversion loss, read by window_kernel; rescore_kernel rewrites the slot as `ok`
     rc = convert_scaled(Q, M, D, qh, qn2, qres2, (unsigned*)qst, 0, st);
     if (rc) return rc;

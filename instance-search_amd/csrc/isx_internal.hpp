@@ -6,6 +6,11 @@
 
 namespace isx {
 
+// Zero `bytes` (a multiple of 4) at a 4-byte aligned device pointer with a KERNEL on `st` (cosine.hip); 0 or ISX_ERR_HIP (error string set, prefixed
+// with `who`).  Every entry zeroes through this and none through hipMemsetAsync: captured into a hipGraph, the memset node zeroes on the first
+// replay only and fills with stale bits on every later one (ROCm 7.0; found by tests/test_gpu_graph_capture.py, docs/rounds/r16.md).
+int zero_words_async(void* p, size_t bytes, hipStream_t st, const char* who);
+
 // ---- the fp32 GEMM of gemm.hip ----------------------------------------------------------------------------------------------------
 // Epilogue modes (the EPI template argument of cosine_gemm_kernel) and the arguments of each mode.
 constexpr int kEpiScores = 0, kEpiFilter = 1, kEpiConv = 2, kEpiMaskedGrad = 3;

@@ -71,6 +71,13 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
+// The output is zeroed by a kernel, not by hipMemsetAsync: captured into a hipGraph, the memset node zeroes on the first replay only and fills
+// with stale bits on every later one (ROCm 7.0; tests/test_gpu_graph_capture.py::test_captured_and_replayed[prep_channel_moments_u8]).
+__global__ __launch_bounds__(256) void zero_moments_kernel(unsigned long long* __restrict__ moments, int n) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i < n) moments[i] = 0;
+}
+
 __global__ __launch_bounds__(kThreads) void channel_moments_kernel(const uint8_t* __restrict__ img, int64_t N, int gpc,
                                                                    unsigned long long* __restrict__ moments) {
     __shared__ unsigned long long part[kThreads / 64][6];
@@ -160,8 +167,10 @@ ISXP_API int isxp_channel_moments_u8(const uint8_t* img, int64_t B, int H, int W
     if (!img || !moments) return fail(ISXP_ERR_ARG, "isxp_channel_moments_u8: null pointer (img, moments)");
     if ((uintptr_t)moments % 8) return fail(ISXP_ERR_ARG, "isxp_channel_moments_u8: moments must be 8-B aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(moments, 0, (size_t)B * 6 * sizeof(int64_t), st) != hipSuccess)
-        return fail(ISXP_ERR_HIP, "isxp_channel_moments_u8: hipMemsetAsync failed");
+    const int n_mom = (int)B * 6;                             // B <= 65535
+    hipLaunchKernelGGL(zero_moments_kernel, dim3((unsigned)((n_mom + 255) / 256)), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(moments), n_mom);
+    const hipError_t ez = hipGetLastError();
+    if (ez != hipSuccess) return fail(ISXP_ERR_HIP, "isxp_channel_moments_u8: zero fill failed: %s", hipGetErrorString(ez));
     const int64_t groups = N / 48;
     int64_t chunks = (kTargetBlocks + B - 1) / B;
     const int64_t most = (groups + kMinGroups - 1) / kMinGroups;

@@ -15,7 +15,10 @@ no information there, everything serialises.  A Case here runs its entry on a fr
 
 Decoys are never NaN and never poison, and every operand a kernel derives an address from (indices, labels, rows, matrices) is in range as a
 decoy: a stream-order mistake shows as wrong bits, not as a fault.  Every case asserts on the CPU that its reference gives something else
-for the decoys than for the real operands."""
+for the decoys than for the real operands.
+
+Case.run_captured (tests/test_gpu_graph_capture.py) runs the same case a third way: the call captured into a HIP graph on a fresh stream under
+the decoys, then the one graph replayed on decoys, on boosted operands, on the real operands over those leftovers and on poisoned buffers."""
 import functools
 import time
 import types
@@ -179,6 +182,102 @@ class Case(object):
         finally:
             torch.cuda.synchronize()                                        # also after a failure: nothing of S is pending when the regions go out of scope
         return took
+
+    # ---- captured into a HIP graph and replayed (tests/test_gpu_graph_capture.py) ----------------------------------------------------------------
+    def _dev(self, data):
+        return {n: torch.from_numpy(_flat_ints(a)).cuda() for n, a in data.items() if a is not None}
+
+    def _fresh(self, r, res=()):
+        """Outputs their poison, workspaces their pattern, and whatever the wrapper allocated itself a value no result holds."""
+        for n in list(self.outs) + list(self.ws):
+            r[n].raw().fill_(r[n].poison)
+        for t in res:
+            t.fill_(float("nan") if t.is_floating_point() else G.POISON_U8 if t.dtype == torch.uint8 else G.POISON_I32)
+
+    def _nothing_executed(self, r, decoy):
+        """After the capture has closed: the captured call ran nothing.  Every output is entirely poison, every workspace its pattern, every
+        in-place operand its decoy, every guard intact."""
+        for n in list(self.outs) + list(self.ws):
+            left = r[n].unwritten()
+            assert left == r[n].n, ("the captured call EXECUTED: %d of %d elements of %s written before any replay" % (r[n].n - left, r[n].n, n), "capture")
+        for n in self.io:
+            assert torch.equal(r[n].raw(), decoy[n]), ("the captured call EXECUTED: the in-place operand %s changed before any replay" % n, "capture")
+        self._guards(r, "capture")
+
+    def _guards(self, r, what):
+        for n, x in r.items():
+            assert x is None or x.guards_intact(), ("store outside", n, what)
+
+    def _replayed(self, g, r, what):
+        g.replay()
+        torch.cuda.synchronize()
+        self._guards(r, what)
+
+    def _wrote_something(self, r, what):
+        for n in self.outs:
+            assert r[n].unwritten() < r[n].n, ("left poisoned: the replay wrote nothing of %s" % n, what)
+
+    def run_captured(self):
+        """The case captured into a graph on a fresh stream and replayed -- after the caller's run_plain(), which has loaded the code objects.
+
+        C ABI:  1. capture under DECOYS (nothing but the call inside the capture; the return code is asserted after it has closed; nothing executed)
+                2. replay on the decoys: real leftovers in outputs and workspaces
+                3. (cases with a workspace) replay on BOOSTED operands, every fp32 operand x 4: leftovers that beat every real score
+                4. real operands, outputs NOT re-poisoned, workspaces NOT refilled: replay, the reference's bits ("replay on stale state")
+                5. outputs poisoned, workspaces refilled, in-place operands restored: replay, the reference's bits ("replay on poisoned state")
+        Wrappers (level "ops"): capture under decoys (what the wrapper allocates lies in the graph's pool and comes back as its results), nothing
+        of `outs` written; real operands, replay, verify; re-poison, replay, verify.
+        An AssertionError leaves the device drained; any other exception launches nothing more (the caller stops its pass)."""
+        from isx._lib import IsxError
+        want = self.expected()
+        r = self._regions(self.decoys())
+        real, decoy = self._dev(self.ins), self._dev(self.decoys())
+        boosted = self._dev({n: a * a.dtype.type(4) if a is not None and a.dtype == np.float32 else a for n, a in self.ins.items()})
+        torch.cuda.synchronize()
+        stream, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+        refused, res = None, {}
+        try:
+            with torch.cuda.graph(g, stream=stream, capture_error_mode="global"):
+                try:
+                    res, _ = self._invoke(r, stream)
+                except (AssertionError, IsxError) as e:                     # a non-zero return code: reported once the capture has closed
+                    refused = e
+            torch.cuda.synchronize()
+            if refused is not None:
+                raise AssertionError("the call was refused under capture: %r" % (refused,)) from refused
+            self._nothing_executed(r, decoy)
+            if self.level == "abi":
+                self._replayed(g, r, "replay on decoys")
+                if self.ws:
+                    for n, t in boosted.items():
+                        r[n].raw().copy_(t)
+                    self._replayed(g, r, "replay on boosted operands")
+                for n, t in real.items():
+                    r[n].raw().copy_(t)
+                self._replayed(g, r, "replay on stale state")
+                self._wrote_something(r, "replay on stale state")
+                post, self.post = self.post, None                           # Case.post runs once, after the last replay
+                try:
+                    self._verify(r, {}, want, "replay on stale state")
+                finally:
+                    self.post = post
+            else:
+                for n, t in real.items():
+                    r[n].raw().copy_(t)
+                self._replayed(g, r, "replay on real operands")
+                self._wrote_something(r, "replay on real operands")
+                self._verify(r, res, want, "replay on real operands")
+            self._fresh(r, res.values())
+            for n in self.io:
+                r[n].raw().copy_(real[n])
+            self._replayed(g, r, "replay on poisoned state")
+            self._wrote_something(r, "replay on poisoned state")
+            self._verify(r, res, want, "replay on poisoned state")
+        except AssertionError:
+            torch.cuda.synchronize()                                        # nothing of the replays is pending when the regions go out of scope
+            raise
+        finally:
+            del res, g
 
 
 @functools.lru_cache(maxsize=None)

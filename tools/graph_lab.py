@@ -1,4 +1,5 @@
-"""Lab: the 1024-image trunk pass (49 launches) eager vs replayed from a HIP graph (torch.cuda.CUDAGraph capture of the same calls)."""
+"""Lab: the 1024-image trunk pass (49 launches) eager vs replayed from a HIP graph (torch.cuda.CUDAGraph capture of the same calls).
+The assertion that a replay gives eager's bits is tests/test_gpu_graph_capture.py::test_trunk_pass_replayed (two 64 x 64 images)."""
 import os
 import sys
 import time
