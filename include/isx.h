@@ -35,6 +35,8 @@
  *     (kh, kw, ci) in chunks of ISX_CONV_CHUNK terms -- that chain inside a chunk, the chunk
  *     sums added in order into a second fp32 accumulator (tot = tot + chain_c), then the
  *     epilogue on tot.  The 7x7 stem cuts after filter rows 2 and 5 (63 + 63 + 21 terms).
+ *   - operands may exceed 2^31 elements and 4 GiB except where an entry states a limit (and refuses, ISX_ERR_ARG, before any launch);
+ *     tests/test_gpu_large_tensors.py holds this for every function below whose last parameter is `isx_stream_t stream`
  */
 #ifndef ISX_H_
 #define ISX_H_
@@ -255,7 +257,8 @@ int isx_region_topk(const float* cls, int64_t B, int K, int Hp, int Wp, int k, i
  * Windows with flat_idx < 0 or past the map produce zero rows (+0).  Sum of squares: thread t of 1024 adds elements t, t + 1024, ... of the
  * (C,h,w) row, butterfly per wave, the 16 wave sums in order; the NHWC entry walks its (h,w,C) row in float4s t, t + 1024, ... and adds the
  * four squares one by one -- another order, and another element order of the row.  A row's bits depend on its window alone.  The caller applies the Linear ONCE to all B*k rows
- * (the 100352 x D weight is then streamed once per batch, not once per window as in the reference). */
+ * (the 100352 x D weight is then streamed once per batch, not once per window as in the reference).  B < 65536 (one image per grid row;
+ * both layouts), C*kh*kw < 2^31. */
 int isx_region_gather_l2(const float* fmap, int64_t B, int C, int Hf, int Wf, int kh, int kw, const int64_t* flat_idx, int k,
                          int Wp, const float* shift, float eps, float* rows, isx_stream_t stream);
 
@@ -577,6 +580,7 @@ int isx_conv3x3_s2_col2im_nhwc(const float* dcol, int64_t B, int H, int W, int C
  * summation tree, no atomics.  taps = 1: 1x1 convolution with `stride` (no padding); taps = 9: 3x3, padding 1, `stride`.
  * x: (B,H,W,Cin), dz: (B,Ho,Wo,Cout), dw: (leaves,S,Cout,taps,Cin) -- per partial the layout of the forward kernels' weights;
  * db: (leaves,S,Cout) or NULL.  Pixels are summed in index order (k-ordered fp32 fma chain).  Cin, Cout % 64 == 0; B % leaves == 0.
+ * Limits (refused): leaves <= 4096; leaves * S <= 65535 (the grid's z extent); B*H*W < 2^31 (32-bit pixel indices).
  * The split rule: with K the output pixels of ONE leaf, nk = ceil(K / 32) k-tiles of 32 pixels and kt_per = ceil(nk / S), split s owns the
  * pixels [32 s kt_per, min(K, 32 (s + 1) kt_per)) of its leaf; a split past the last k-tile is EMPTY and writes zeros (dw and db).
  * The order: dw[l][s][co][tap][ci] is ONE fma chain from +0 over that split's pixels, ascending, of dz[p][co] * x[src(p, tap)][ci], with

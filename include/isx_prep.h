@@ -17,6 +17,8 @@
  *     result.  It has no debug hooks and no calls outside this contract
  *   - return 0 = ISXP_OK, <0 = error; isxp_last_error() gives a thread-local message that
  *     starts with the name of the entry
+ *   - operands may exceed 2^31 elements and 4 GiB except where an entry states a limit;
+ *     tests/test_gpu_large_tensors.py holds this (14 270 images of 224 x 224: 2.1 GB of bytes)
  */
 #ifndef ISX_PREP_H_
 #define ISX_PREP_H_

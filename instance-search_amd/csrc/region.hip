@@ -227,7 +227,7 @@ ISX_API int isx_best_location_desc(const float* cls, int64_t B, int K, int Hp, i
 
 ISX_API int isx_region_topk(const float* cls, int64_t B, int K, int Hp, int Wp, int k, int64_t* flat_idx, float* score,
                             isx_stream_t stream) {
-    ISX_REQUIRE(B >= 0 && B < 65536 && K > 0 && Hp > 0 && Wp > 0 && k > 0, "isx_region_topk: bad shape B=%lld K=%d Hp=%d Wp=%d k=%d", (long long)B, K, Hp, Wp, k);
+    ISX_REQUIRE(B >= 0 && B < (1ll << 31) && K > 0 && Hp > 0 && Wp > 0 && k > 0, "isx_region_topk: bad shape B=%lld K=%d Hp=%d Wp=%d k=%d", (long long)B, K, Hp, Wp, k);
     if (B == 0) return ISX_OK;
     const int64_t P = (int64_t)Hp * Wp;
     ISX_REQUIRE(P <= 4096, "isx_region_topk: Hp*Wp=%lld exceeds 4096 locations", (long long)P);
@@ -265,7 +265,7 @@ ISX_API int isx_best_location_desc_nhwc(const float* cls, int64_t B, int K, int 
 
 ISX_API int isx_region_topk_nhwc(const float* cls, int64_t B, int K, int Hp, int Wp, int k, int64_t* flat_idx, float* score,
                                  isx_stream_t stream) {
-    ISX_REQUIRE(B >= 0 && B < 65536 && K > 0 && Hp > 0 && Wp > 0 && k > 0, "isx_region_topk_nhwc: bad shape B=%lld K=%d Hp=%d Wp=%d k=%d", (long long)B, K, Hp, Wp, k);
+    ISX_REQUIRE(B >= 0 && B < (1ll << 31) && K > 0 && Hp > 0 && Wp > 0 && k > 0, "isx_region_topk_nhwc: bad shape B=%lld K=%d Hp=%d Wp=%d k=%d", (long long)B, K, Hp, Wp, k);
     if (B == 0) return ISX_OK;
     const int64_t P = (int64_t)Hp * Wp;
     ISX_REQUIRE(P <= 4096, "isx_region_topk_nhwc: Hp*Wp=%lld exceeds 4096 locations", (long long)P);
