@@ -542,11 +542,20 @@ def parse_scales(arg):
     return out
 
 
+def parse_scale_pixels(arg):
+    """'normalised' | 'u8': what train.classif_regions resizes for its further scales (multi_scale_items)."""
+    if arg not in ('normalised', 'u8'):
+        raise ValueError("--scale-pixels takes 'normalised' or 'u8', got %r" % (arg,))
+    return arg
+
+
 def training_cli(argv, P, run, what):
     """`python -m train.<approach> --dataset=<folder | synthetic:...> [--model=] [--device=] [--epochs=] [--classif-model=] [--preload-net=]
-    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=] [--bn-model=] [--scales=] [--augment=]`
+    [--save-dir=] [--feature-dim=] [--batch-size=] [--micro-batch=] [--lr=] [--seed=] [--loss-int=] [--bn-model=] [--scales=] [--augment=]
+    [--scale-pixels=]`
     (--scales: comma list of shorter-side sizes of train.classif_regions, 0 = the image as is; --augment=reference | rot,hr,vr,hsr,vsr,hflip: the
-    reference's random_affine_noisy_cv on every training image of every batch, default off): the reference's training scripts take everything from their
+    reference's random_affine_noisy_cv on every training image of every batch, default off; --scale-pixels=u8: train.classif_regions resizes
+    the decoded 8-bit image and normalises afterwards, default normalised): the reference's training scripts take everything from their
     *_p.py file (edit and run); the same fields can be given here instead."""
     import getopt
     import sys
@@ -554,7 +563,8 @@ def training_cli(argv, P, run, what):
             'classif-model': ('classif_model', str), 'preload-net': ('preload_net', str), 'save-dir': ('save_dir', str),
             'feature-dim': ('feature_dim', int), 'batch-size': ('train_batch_size', int), 'micro-batch': ('train_micro_batch', int),
             'lr': ('train_lr', float), 'seed': ('train_seed', int), 'loss-int': ('train_loss_int', int), 'bn-model': ('bn_model', str),
-            'scales': ('train_sub_scales', parse_scales), 'augment': ('train_trans', parse_augment)}
+            'scales': ('train_sub_scales', parse_scales), 'augment': ('train_trans', parse_augment),
+            'scale-pixels': ('train_scale_pixels', parse_scale_pixels)}
     try:
         opts, _ = getopt.getopt(argv, '', ['help'] + [k + '=' for k in spec])
     except getopt.GetoptError as e:

@@ -197,14 +197,40 @@ def scale_image(im, size):
     return torch.nn.functional.interpolate(im.unsqueeze(0), size=(h, w), mode='bicubic', align_corners=False)[0].contiguous()
 
 
-def multi_scale_items(train_set, scales):
-    """(image, label, path) -> ([image at every scale of `scales`], label, path); raw uint8 images are normalised first."""
+def scale_image_u8(im_u8, size):
+    """A raw (H, W, 3) uint8 image with its shorter side brought to `size` (None: as is), as the reference's scale_cv does it: the cubic resize
+    of the 8-bit image (isx.scale, the pixels defined in include/isx_scale.h), on the device when P.cuda_device >= 0 and on the host otherwise
+    -- the same bytes."""
+    from isx import scale
+    if size is None:
+        return im_u8
+    hw = scale.short_side_size(im_u8.shape[0], im_u8.shape[1], size)
+    if hw == tuple(im_u8.shape[:2]):
+        return im_u8
+    if P.cuda_device >= 0:
+        with torch.cuda.device(P.cuda_device):
+            return scale.resize_cubic_u8(im_u8.unsqueeze(0).cuda(), hw)[0].cpu()
+    return scale.resize_cubic_u8_host(im_u8.unsqueeze(0), hw)[0]
+
+
+def multi_scale_items(train_set, scales, pixels='normalised'):
+    """(image, label, path) -> ([image at every scale of `scales`], label, path).  pixels='normalised' (the default): raw uint8 images are
+    normalised first and the fp32 tensor is interpolated (scale_image).  pixels='u8': the raw uint8 image is resized (scale_image_u8) and
+    normalised afterwards, the reference's order; images that are not raw uint8 are refused in that mode."""
     from ._common import normalise_u8_batch
 
     def norm(im):
         return normalise_u8_batch(im.unsqueeze(0), -1)[0] if im.dtype == torch.uint8 else im
 
-    items = [([scale_image(norm(im), s) for s in scales], lab, path) for im, lab, path in train_set]
+    if pixels == 'u8':
+        for im, _, path in train_set:
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                raise ValueError("pixels='u8' needs raw (H,W,3) uint8 images, got %s %s for %s" % (tuple(im.shape), im.dtype, path))
+        items = [([norm(scale_image_u8(im, s)) for s in scales], lab, path) for im, lab, path in train_set]
+    elif pixels == 'normalised':
+        items = [([scale_image(norm(im), s) for s in scales], lab, path) for im, lab, path in train_set]
+    else:
+        raise ValueError("pixels must be 'normalised' or 'u8', got %r" % (pixels,))
     for ims, _, path in items:
         shapes = [tuple(im.shape) for im in ims]
         if len(set(shapes)) != len(shapes):               # e.g. scales (None, 224) on a 224-pixel image: the same windows would be trained on twice
@@ -218,12 +244,14 @@ def run(dataset_full=None):
     [identity, scale_cv(224)])."""
     from ._common import is_augmenter, load_training_sets
     if is_augmenter(getattr(P, 'train_trans', None)):
-        # the reference's per-scale transform lists put a resize (scale_cv) AFTER the warp: the augmenter kernel has no such stage
+        # not built: the reference resizes every scale at load and warps each stored scale per batch (one isx_affine_noisy_u8 call per scale on
+        # the uint8 scales of pixels='u8' would do it); the message below is older than that reading of the reference
         raise NotImplementedError('train.classif_regions: augmentation is not supported here -- the per-scale transform lists of the reference '
                                   '(classif_regions_p.py) resize after the warp, which isx_affine_noisy_u8 does not do; run with --augment=off')
     train_set, test_train_set, test_set = load_training_sets(P, dataset_full or P.dataset_full, labels)
     scales = list(getattr(P, 'train_sub_scales', None) or [None, 224])
-    return main(multi_scale_items(train_set, scales), test_train_set, test_set)
+    # P.train_scale_pixels (--scale-pixels): 'u8' resizes the decoded 8-bit image and normalises afterwards, as the reference does
+    return main(multi_scale_items(train_set, scales, getattr(P, 'train_scale_pixels', None) or 'normalised'), test_train_set, test_set)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,7 @@
 """Parameters of the sub-region classifier training (reference train/classif_regions_p.py:53-94).  The reference's cv2 augmentation and its
 scale_cv are not part of this package: the training images are pre-processed once (train_pre_proc = True) and the second scale is a bicubic
-interpolation of the normalised tensor (train_sub_scales: None = the image as is, an int = shorter side to that size)."""
+interpolation of the normalised tensor (train_sub_scales: None = the image as is, an int = shorter side to that size), or, with
+train_scale_pixels = 'u8', isx.scale's cubic resize of the decoded 8-bit image, normalised afterwards."""
 from .params import Params
 
 P = Params(cnn_model='AlexNet', feature_size2d=(6, 6), feature_dim=464,
