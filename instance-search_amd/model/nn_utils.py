@@ -76,9 +76,9 @@ def extract_layers(net):
 # A/B switches (environment).  ISX_CONV1X1=0 sends the 1x1 trunk convolutions back to MIOpen.  ISX_CONV3X3: "auto"
 # (default) runs the implicit-GEMM kernel where it wins on MI355X -- every 3x3 convolution of a BN-folded residual block (round 2,
 # with the buffer-instruction epilogue: 1.93-1.98 ms against MIOpen's igemm + zero fill + separate epilogue pass 2.05-2.15 ms at
-# Cin >= 256, B = 1024; ResNet-50 extraction +2-3 % at B = 256 and at 448x448) and stand-alone convolutions with Cin <= 128; the
-# 13x13 AlexNet layers (192->384, 384->256, 256->256) stay with MIOpen (-5 % otherwise) -- "1" everywhere, "0" never, an integer
-# N > 1: Cin <= N.
+# Cin >= 256, B = 1024; ResNet-50 extraction +2-3 % at B = 256 and at 448x448) and stand-alone convolutions BEHIND A BATCHNORM with
+# Cin <= 128 -- "1" everywhere, "0" never, an integer N > 1: Cin <= N.  (The 13x13 AlexNet layers, 192->384, 384->256, 256->256, have no
+# BatchNorm: they are ISX_ALEX's, below, which re-measured the -5 % once noted here with the ReLU fused: +11 %.)
 _CONV3X3_MODE = os.environ.get("ISX_CONV3X3", "auto")
 _IMPLICIT_GEMM_3X3 = _CONV3X3_MODE != "0"
 _GEMM_1X1 = os.environ.get("ISX_CONV1X1", "1") != "0"
@@ -90,9 +90,23 @@ if not (_GEMM_1X1 and _FUSED_STEM and _FUSE_EXPAND and _FUSE_PROJECTION and _CON
     warnings.warn("libisx A/B switches are set (ISX_CONV1X1 / ISX_CONV3X3 / ISX_STEM / ISX_FUSE_EXPAND / ISX_FUSE_PROJECTION): some trunk "
                   "convolutions run on MIOpen or unfused in this process -- a measurement aid, not the product path")
 
+# ISX_ALEX: the convolutions without a BatchNorm behind them and the MaxPool2d(3, 2) of an AlexNet-style `features` (isx.backbones.alexnet,
+# model.ModelDefinition.Maxnet).  "1": every one of them runs on libisxalex (isx/alex.py: general K x K convolution with the trunk's canonical sum,
+# un-padded 3 / 2 max-pool) or, the 3x3 / padding 1 layers with Cin % 32 == 0, on libisx's isx_conv3x3_nhwc -- no torch convolution or pool on
+# the GPU, descriptors that do not depend on the batch.  "0": the modules as they were (MIOpen, torch ReLU, torch max_pool2d), bit for bit.  "auto"
+# (default): per layer kind, native where tools/alex_lab.py measured it no slower than MIOpen's route by more than that route's own spread
+# (_ALEX_AUTO_KINDS; DESIGN 4, "AlexNet trunk").  Read at fold time and at every forward.  Measured at B = 256, 224 x 224 (ms per layer kind, HIP route
+# against MIOpen's with its min-max spread): 11x11 / 4 0.513 : 0.573 (0.091), 5x5 1.022 : 0.978 (0.111) -- 4 % behind, inside the spread, and ahead
+# again with the pool behind it --, the three 13x13 3x3 layers 1.486 : 1.670 (0.149), the three pools 0.141 : 0.235 (0.160); extraction 84.2 k : 75.6 k
+# images/s.  Every kind is taken.  A kernel size outside these (conv1, conv7, ...) has not been measured and goes native under "1" only.
+_ALEX_MODE = os.environ.get("ISX_ALEX", "auto")
+_ALEX_AUTO_KINDS = frozenset(("conv11", "conv5", "conv3", "pool"))
+
 # Convolutions that ran on torch's conv2d (MIOpen) on a GPU tensor in this process, as {(kernel, stride, Cin, Cout): calls}: the ResNet
-# trunks leave it empty (every layer is a libisx kernel); AlexNet's 11x11 / 5x5 layers and its 3x3 layers at 13x13 with Cin > 128, a 3x3
-# with Cin % 32 != 0, grouped / dilated convolutions and stand-alone strided 1x1 layers land here ("what still runs on MIOpen").
+# trunks leave it empty (every layer is a libisx kernel), and so does an AlexNet-style trunk under ISX_ALEX=1; the AlexNet layer kinds that
+# ISX_ALEX=auto leaves with MIOpen (see _ALEX_AUTO_KINDS), a 3x3 with Cin % 32 != 0 behind a BatchNorm, grouped / dilated convolutions and
+# stand-alone strided 1x1 layers land here ("what still runs on MIOpen").  Under ISX_ALEX=0 the AlexNet layers are plain torch
+# modules again and are not counted.
 TORCH_CONV_CALLS = {}
 
 
@@ -336,6 +350,92 @@ class _FusedBlock(nn.Module):
         return self.convs[-1](y, idt)
 
 
+def _alex_native(kind):
+    return _ALEX_MODE == "1" or (_ALEX_MODE == "auto" and kind in _ALEX_AUTO_KINDS)
+
+
+def _gpu_inference_nhwc(x):
+    return (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+class _AlexConv(nn.Module):
+    """A convolution with no BatchNorm behind it (+ the ReLU that follows) of an AlexNet-style trunk.  On channels-last GPU activations without
+    an autograd graph, where ISX_ALEX takes its layer kind: ONE call with bias and ReLU fused -- isx.alex.conv2d_nhwc, or isx.ops.conv3x3_nhwc for a
+    3x3 / padding 1 layer with Cin % 32 == 0 (the same sum: either library gives the same bits).  Everywhere else (CPU, training, ISX_ALEX kinds left
+    with MIOpen) the two modules it was built from, called as the Sequential called them."""
+
+    def __init__(self, conv, act):
+        super().__init__()
+        import copy
+        self.conv = copy.deepcopy(conv)
+        self.act = copy.deepcopy(act)                       # the nn.ReLU behind the convolution, or None
+        k = conv.kernel_size[0]
+        self.libisx_3x3 = (k == 3 and tuple(conv.padding) == (1, 1) and conv.stride[0] in (1, 2) and conv.in_channels % 32 == 0)
+        self.kind = "conv%d" % k                             # the layer kinds of ISX_ALEX=auto: conv11, conv5, conv3 (and pool)
+        if conv.bias is None:
+            self.register_buffer("no_bias", torch.zeros(conv.out_channels), persistent=False)
+
+    def w_ohwi(self):
+        """(Cout,K,K,Cin) copy of the weight; follows the weight (see _derived)."""
+        w = self.conv.weight
+        return _derived(self, '_c_w_ohwi', (w,), lambda: w.detach().permute(0, 2, 3, 1).contiguous())
+
+    def forward(self, x):
+        c = self.conv
+        if _alex_native(self.kind) and _gpu_inference_nhwc(x):
+            bias = c.bias if c.bias is not None else self.no_bias
+            if self.libisx_3x3:
+                from isx import ops
+                return ops.conv3x3_nhwc(x, self.w_ohwi(), bias, c.stride[0], None, self.act is not None)
+            from isx import alex
+            if x.data_ptr() % 16:
+                # a view into a larger batch whose images are no multiple of 16 bytes (Cin = 3): the kernel wants its base pointer aligned
+                x = x.clone(memory_format=torch.channels_last)
+            return alex.conv2d_nhwc(x, self.w_ohwi(), bias, c.stride[0], c.padding[0], self.act is not None)
+        y = c(x)
+        if y.is_cuda:
+            _note_torch_conv(c)
+        return y if self.act is None else self.act(y)
+
+
+class _AlexPool(nn.Module):
+    """MaxPool2d(3, stride 2) without padding, dilation or ceil mode: isx.alex.maxpool3s2 (torch's bits) on channels-last GPU activations without an
+    autograd graph where ISX_ALEX takes the pool, the module itself everywhere else."""
+    kind = "pool"
+
+    def __init__(self, pool):
+        super().__init__()
+        import copy
+        self.pool = copy.deepcopy(pool)
+
+    def forward(self, x):
+        if _alex_native(self.kind) and _gpu_inference_nhwc(x):
+            # "auto" picks a route per shape; under "1" a map the kernel does not take is an error (isx.alex raises), never a quiet torch pool
+            if _ALEX_MODE == "1" or (x.shape[1] % 4 == 0 and x.shape[2] >= 3 and x.shape[3] >= 3):
+                from isx import alex
+                return alex.maxpool3s2(x)
+        return self.pool(x)
+
+
+def _is_alex_conv(m):
+    from isx import alex
+    return type(m) is nn.Conv2d and alex.conv2d_applicable(m)
+
+
+def _is_alex_pool(m):
+    return (type(m) is nn.MaxPool2d and m.kernel_size in (3, (3, 3)) and m.stride in (2, (2, 2)) and m.padding in (0, (0, 0))
+            and m.dilation in (1, (1, 1)) and not m.ceil_mode and not m.return_indices)
+
+
+def alex_route_active(features):
+    """Does ISX_ALEX send a layer of this trunk to a HIP kernel?  What makes folding a trunk WITHOUT BatchNorm worth it
+    (train._common.prepare_for_inference): under "0", and under "auto" while no kind is taken, such a trunk stays as it is."""
+    if _ALEX_MODE == "0":
+        return False
+    return any((_is_alex_conv(m) and _alex_native("conv%d" % m.kernel_size[0])) or (_is_alex_pool(m) and _alex_native("pool")) for m in features)
+
+
 class _ChannelsLastEntry(nn.Module):
     """First module of a folded trunk: a GPU fp32 image batch enters in channels-last memory, so that every activation
     behind it is the row-major (pixels, channels) matrix the hand-written convolution kernels (and MIOpen's NHWC kernels)
@@ -388,6 +488,16 @@ def fold_batch_norm(features, fuse_epilogues=True):
                 i += 1
             else:
                 out.append(conv)
+            continue
+        if fuse_epilogues and _ALEX_MODE != "0" and _is_alex_conv(m):
+            # AlexNet-style layer: convolution (+ ReLU) without a BatchNorm -> one module that ISX_ALEX routes to a HIP kernel with the epilogue fused
+            act = mods[i + 1] if i + 1 < len(mods) and type(mods[i + 1]) is nn.ReLU else None
+            out.append(_AlexConv(m, act))
+            i += 1 if act is None else 2
+            continue
+        if fuse_epilogues and _ALEX_MODE != "0" and _is_alex_pool(m):
+            out.append(_AlexPool(m))
+            i += 1
             continue
         out.append(fold_block(m) if isinstance(m, (models.Bottleneck, models.BasicBlock)) else copy.deepcopy(m))
         i += 1

@@ -651,9 +651,10 @@ def load_weights(net, fname):
 
 def prepare_for_inference(net, P):
     """eval mode (+ BatchNorm folding / fused epilogues when P.fold_bn): call once before get_embeddings."""
-    from model.nn_utils import fold_batch_norm, set_net_train
+    from model.nn_utils import alex_route_active, fold_batch_norm, set_net_train
     set_net_train(net, False)
-    if getattr(P, 'fold_bn', False) and any(isinstance(m, torch.nn.BatchNorm2d) for m in net.features.modules()):
+    # (a trunk without BatchNorm -- AlexNet, Maxnet -- is folded where ISX_ALEX sends one of its layers to a HIP kernel: model/nn_utils.py)
+    if getattr(P, 'fold_bn', False) and (any(isinstance(m, torch.nn.BatchNorm2d) for m in net.features.modules()) or alex_route_active(net.features)):
         dev = next(net.parameters()).device
         net.features = fold_batch_norm(net.features).to(dev)
         if dev.type == 'cuda':

@@ -47,11 +47,11 @@ def main():
         # ---- extraction (fp32, channels-last activations, synthetic images)
         x224 = torch.randn(256, 3, 224, 224, device=dev).to(memory_format=torch.channels_last)
         x448 = torch.randn(128, 3, 448, 448, device=dev).to(memory_format=torch.channels_last)
-        from model.nn_utils import fold_batch_norm
+        from model.nn_utils import alex_route_active, fold_batch_norm
 
         def cl(m):
             m = m.eval()
-            if any(isinstance(x, torch.nn.BatchNorm2d) for x in m.features.modules()):
+            if any(isinstance(x, torch.nn.BatchNorm2d) for x in m.features.modules()) or alex_route_active(m.features):     # (as train._common.prepare_for_inference)
                 m.features = fold_batch_norm(m.features)        # inference trunk: BN folded, fused epilogues
             return m.to(dev).to(memory_format=torch.channels_last)
         g = cl(TuneClassif(backbones.resnet50(pretrained=True), 464))
