@@ -681,7 +681,9 @@ int isx_tree_sum_rows(const float* rows, int L, int64_t stride, int64_t n, float
 void isx_debug_set_gemm_cfg(int c);
 /* Trunk convolution tiles: 0 = 128x128, 2 = 128x64, 3 = 64x64 (3x3 and dual 1x1 kernels); 7 = automatic
  * without the 64x64 tails; 8 = automatic with the pixel-major row order on every 3x3 shape (no position-major
- * tiles on small maps); 9 = the general 1x1 path instead of the streaming kernel; -1 = automatic.
+ * tiles on small maps); 9 = the general 1x1 path instead of the streaming kernel; 10 = automatic with the
+ * position-major tiles in raster order instead of longest first (nine-, six-, four-tap positions); 11 = 10
+ * with the 128x128 shape forced as under 0; -1 = automatic.
  * Initial value from the environment variable ISX_DEBUG_CONV_CFG. */
 void isx_debug_set_conv_cfg(int c);
 /* fp16 filter GEMM of isx_cosine_topk_fast: 0 = 128x128, 1 = 256x256, 2 = 256x256 register-staged, -1 = automatic. */

@@ -11,6 +11,7 @@
 // (conv3x3_tail_kernel, conv1x1_dual_tail_kernel; conv1x1_tail_kernel in gemm.hip); isx_debug_set_conv_cfg(7) turns that off (A/B).
 // The 128x128 launches of isx_conv3x3_nhwc on small maps number their rows position-major and skip the padding taps (conv3x3_tile.hpp;
 // eligibility and the measured cut-off at kPosMajorMaxP below); isx_debug_set_conv_cfg(8) keeps the pixel-major order (A/B, tests).
+// Their tiles run longest first (nine-tap positions, then six, then four); isx_debug_set_conv_cfg(10) keeps them in raster order (A/B, tests; 11: with the 128x128 shape forced).
 //
 // Reference call sites: the torchvision ResNet `features` trunk built by model/ModelDefinition.py, split by
 // model/nn_utils.py:56-71 and run from model/siamese.py:20,107,151.
@@ -232,8 +233,9 @@ static void launch_dual(const float* t, const float* x, int64_t M, const float* 
                        bias, relu);
 }
 
-static std::atomic<int> g_force_conv_cfg{[] { const char* e = getenv("ISX_DEBUG_CONV_CFG"); return e ? atoi(e) : -1; }()};       // debug / A-B hook
+static std::atomic<int> g_force_conv_cfg{[] { const char* e = getenv("ISX_DEBUG_CONV_CFG"); const int c = e ? atoi(e) : -1; return c == 11 ? 0 : c; }()};       // debug / A-B hook
 static std::atomic<int> g_pos_major{[] { const char* e = getenv("ISX_DEBUG_CONV_CFG"); return !(e && atoi(e) == 8); }()};     // 0: pixel-major row order everywhere (cfg 8)
+static std::atomic<int> g_pos_raster{[] { const char* e = getenv("ISX_DEBUG_CONV_CFG"); return e && (atoi(e) == 10 || atoi(e) == 11); }()};      // 1: position-major tiles in raster order (cfg 10, 11)
 
 // Largest output map (Ho * Wo) that runs in the position-major row order (conv3x3_tile.hpp).  MEASURED, not assumed: the six 3x3 shapes of
 // ResNet-50 at B = 1024, both row orders alternating in one process (ms per launch, pixel-major -> position-major; share of the (pixel, tap)
@@ -253,6 +255,7 @@ int64_t conv3x3_pos_major_rows(int64_t B, int H, int W, int Cin, int Ho, int Wo,
                            (128ll * H * W + 2 * W + 4) * Cin * 4 < (1ll << 32) && 128ll * P * Cout * 4 < (1ll << 31);
     return pos_major && ((B + 127) / 128 * P * 2) * tiles_n64 < (1ll << 31) ? (B + 127) / 128 * P * 128 : 0;        // (tile count of the virtual rows)
 }
+int conv3x3_pos_major_raster() { return g_pos_raster; }
 
 // steady-state efficiency of the 3x3 tile shapes (128x128, -, 128x64, 64x64) for pick_tile_cfg: forward and input gradient
 static const float kEff3x3[4] = {0.90f, 0.0f, 0.865f, 0.87f};
@@ -288,7 +291,7 @@ ISX_API int isx_conv3x3_nhwc(const float* x, int64_t B, int H, int W, int Cin, c
     ISX_REQUIRE((((uintptr_t)x | (uintptr_t)w_ohwi) % 16) == 0, "isx_conv3x3_nhwc: x and w must be 16-B aligned");
     ISX_REQUIRE(y != x && y != residual, "isx_conv3x3_nhwc: y must not alias x or residual");
     Conv3x3Geom g;
-    g.H = H; g.W = W; g.Cin = Cin; g.stride = stride;
+    g.H = H; g.W = W; g.Cin = Cin; g.stride = stride; g.raster = conv3x3_pos_major_raster();
     g.Ho = (H - 1) / stride + 1;
     g.Wo = (W - 1) / stride + 1;
     const int64_t M = B * g.Ho * g.Wo, N = Cout;
@@ -326,7 +329,7 @@ ISX_API int isx_conv3x3_dgrad_nhwc(const float* dz, int64_t B, int H, int W, int
     ISX_REQUIRE((((uintptr_t)dz | (uintptr_t)wt) % 16) == 0, "isx_conv3x3_dgrad_nhwc: dz and wt must be 16-B aligned");
     ISX_REQUIRE(dx != dz && dx != mask, "isx_conv3x3_dgrad_nhwc: dx must not alias an input");
     Conv3x3Geom g;
-    g.H = H; g.W = W; g.Cin = Cout; g.stride = 1; g.Ho = H; g.Wo = W;
+    g.H = H; g.W = W; g.Cin = Cout; g.stride = 1; g.Ho = H; g.Wo = W; g.raster = 0;
     const int64_t M = B * H * W, N = Cin;
     const int best = pick_tile_cfg(M, N, 0, kEff3x3, 0xD);
     hipStream_t st = (hipStream_t)stream;
@@ -372,6 +375,7 @@ ISX_API int isx_conv1x1_dual_nhwc(const float* t, int K1, const float* x, int64_
 ISX_API void isx_debug_set_conv_cfg(int c) {
     isx::g_tail_split = (c != 7);        // 7 = automatic tile choice WITHOUT the 64x64 tails (A/B)
     isx::g_pos_major = (c != 8);         // 8 = automatic tile choice with the pixel-major row order on every 3x3 shape (A/B, tests)
-    g_force_conv_cfg = (c == 7 || c == 8) ? -1 : c;
+    isx::g_pos_raster = (c == 10 || c == 11);        // 10 = automatic tile choice with the position-major tiles in raster order (A/B, tests); 11 = the same under 128x128 tiles (0)
+    g_force_conv_cfg = (c == 7 || c == 8 || c == 10) ? -1 : c == 11 ? 0 : c;
 }
 

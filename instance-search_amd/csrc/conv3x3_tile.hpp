@@ -12,7 +12,7 @@ namespace isx {
 // row order below does skip them).
 // Epilogue: bias (+ residual) + ReLU fused, wave-uniform row pointers.  Replaces conv2 of the torchvision
 // Bottleneck / both convolutions of BasicBlock inside the `features` trunk.
-struct Conv3x3Geom { int H, W, Cin, Ho, Wo, stride; };
+struct Conv3x3Geom { int H, W, Cin, Ho, Wo, stride, raster; };     // raster: position-major tiles in raster order (A/B, tests; read by POSMAJ kernels only)
 
 // ---- position-major row order (inference, small maps: isx_conv3x3_nhwc picks it, conv.hip) -------------------------------------------
 // In the pixel-major order a 128-row tile of a 7x7 map is 2.6 whole images: every tap is padding for SOME of its rows, so the padding
@@ -28,12 +28,39 @@ struct Conv3x3Geom { int H, W, Cin, Ho, Wo, stride; };
 // two orders agree on finite weights only (the oracle's tests use no others).
 // Rows of a tile are H W Cin floats apart in x and P Cout floats apart in y: isx_conv3x3_nhwc admits the order only where 128 such rows
 // stay inside the 32-bit offsets of a buffer descriptor.  Rows with b >= B load image B - 1 again and are not stored.
+// LONGEST TILES FIRST: tiles are no longer equal -- an interior position runs nine taps, an edge six, a corner four -- and a launch that walks the
+// positions in raster order ends on whatever comes last.  Within an image group, tile rank r (the p of the formula above) therefore maps to the
+// position of rank r in descending order of visited taps: the interior positions, then the edges, then the corners, raster order inside each class
+// (pos_major_position: closed form, no table).  Per axis index 0 always loses the tap before it; the last index loses the tap behind it where that tap
+// lies outside the input (stride 1; stride 2 on an odd extent).  n x n outputs at stride 1: (n-2)^2, 4 (n-2), 4 positions; stride 2 on an even
+// input: (n-1)^2, 2 (n-1), 1.  The launch's last tiles -- those the tail split cuts into 64-row tiles -- are then the cheapest positions of the last
+// group.  Only WHICH workgroup computes a tile changes: no bit does.  g.raster (isx_debug_set_conv_cfg(10)) keeps the raster order.
+__device__ __forceinline__ int pos_major_position(const Conv3x3Geom& g, int r) {
+    if (g.raster) return r;
+    const int sh = 1 + (g.Ho > 1 && (g.Ho - 1) * g.stride + 1 > g.H - 1), sw = 1 + (g.Wo > 1 && (g.Wo - 1) * g.stride + 1 > g.W - 1);      // short indices per axis: 0 (and the last)
+    const int fh = g.Ho - sh, fw = g.Wo - sw;           // indices with all three taps: 1 .. fh, 1 .. fw
+    int ho, wo;
+    if (r < fh * fw) {                                  // interior
+        ho = r / fw; wo = r - ho * fw;
+        ++ho; ++wo;
+    } else if ((r -= fh * fw) < sh * fw + fh * sw) {    // edges in raster order: row 0, the two (or one) ends of every full row, the last row
+        if (r < fw) { ho = 0; wo = 1 + r; }
+        else if ((r -= fw) < fh * sw) { ho = 1 + (r >> (sw - 1)); wo = (r & (sw - 1)) ? g.Wo - 1 : 0; }
+        else { ho = g.Ho - 1; wo = 1 + r - fh * sw; }
+    } else {                                            // corners
+        r -= sh * fw + fh * sw;
+        ho = (r >> (sw - 1)) ? g.Ho - 1 : 0; wo = (r & (sw - 1)) ? g.Wo - 1 : 0;
+    }
+    return ho * g.Wo + wo;
+}
 struct PosMajorTile { int B, b0, p, hi0, wi0, kh_lo, kh_n, kw_lo, kw_n; };
 __device__ __forceinline__ PosMajorTile pos_major_tile(const Conv3x3Geom& g, int64_t M, int64_t m0) {
     PosMajorTile t;
     const int P = g.Ho * g.Wo, q = (int)(m0 >> 7), grp = q / P;
     t.B = (int)(M / P);
-    t.p = q - grp * P;
+    // (readfirstlane: behind the branches of the mapping hipcc no longer takes p for wave-uniform and wraps the A loads of the k loop, whose SGPR
+    // offset descends from it, into readfirstlane loops)
+    t.p = __builtin_amdgcn_readfirstlane(pos_major_position(g, q - grp * P));
     t.b0 = grp * 128 + (int)(m0 & 127);
     const int ho = t.p / g.Wo, wo = t.p - ho * g.Wo;
     t.hi0 = ho * g.stride - 1;

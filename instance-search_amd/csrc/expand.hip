@@ -22,7 +22,7 @@ ISX_API int isx_conv3x3_expand_nhwc(const float* x, int64_t B, int H, int W, int
     ISX_REQUIRE((((uintptr_t)x | (uintptr_t)w2_ohwi | (uintptr_t)w3t) % 16) == 0, "isx_conv3x3_expand_nhwc: x, w2 and w3t must be 16-B aligned");
     ISX_REQUIRE(y != x && y != residual, "isx_conv3x3_expand_nhwc: y must not alias x or residual");
     Conv3x3Geom g;
-    g.H = H; g.W = W; g.Cin = Cin; g.stride = stride;
+    g.H = H; g.W = W; g.Cin = Cin; g.stride = stride; g.raster = 0;
     g.Ho = (H - 1) / stride + 1;
     g.Wo = (W - 1) / stride + 1;
     const int64_t M = B * g.Ho * g.Wo;
@@ -46,7 +46,7 @@ ISX_API int isx_conv3x3_expand_dual_nhwc(const float* t, int64_t B, int H, int W
     ISX_REQUIRE((((uintptr_t)t | (uintptr_t)w2_ohwi | (uintptr_t)wcat_t | (uintptr_t)x2) % 16) == 0, "isx_conv3x3_expand_dual_nhwc: t, x2, w2 and wcat_t must be 16-B aligned");
     ISX_REQUIRE(y != t && y != x2, "isx_conv3x3_expand_dual_nhwc: y must not alias an input");
     Conv3x3Geom g;
-    g.H = H; g.W = W; g.Cin = Cin; g.stride = 1; g.Ho = H; g.Wo = W;
+    g.H = H; g.W = W; g.Cin = Cin; g.stride = 1; g.Ho = H; g.Wo = W; g.raster = 0;
     const int64_t M = B * H * W;
     hipLaunchKernelGGL((conv3x3_expand_kernel<4, true>), dim3((unsigned)((M + 63) / 64)), dim3(256), 0, (hipStream_t)stream, t, M, w2_ohwi, g, b2, wcat_t, bias, x2,
                        relu ? 1 : 0, y);
@@ -82,7 +82,7 @@ ISX_API int isx_conv3x3_expand128_nhwc(const float* x, int64_t B, int H, int W, 
     ISX_REQUIRE((((uintptr_t)x | (uintptr_t)w2_ohwi | (uintptr_t)w3t) % 16) == 0, "isx_conv3x3_expand128_nhwc: x, w2 and w3t must be 16-B aligned");
     ISX_REQUIRE(y != x && y != residual, "isx_conv3x3_expand128_nhwc: y must not alias x or residual");
     Conv3x3Geom g;
-    g.H = H; g.W = W; g.Cin = Cin; g.stride = 1; g.Ho = H; g.Wo = W;
+    g.H = H; g.W = W; g.Cin = Cin; g.stride = 1; g.Ho = H; g.Wo = W; g.raster = conv3x3_pos_major_raster();
     const int64_t M = B * H * W;
     const int64_t Mv = conv3x3_pos_major_rows(B, H, W, Cin, H, W, Cout, 2);
     const int64_t rows = Mv > 0 ? Mv : M;

@@ -65,6 +65,7 @@ int pick_tile_cfg(int64_t M, int64_t N, int64_t split, const float* eff, unsigne
 
 // Position-major row order of a 3x3 launch (conv3x3_tile.hpp; conv.hip holds the eligibility and its debug switch): the virtual row count, 0 = pixel-major
 int64_t conv3x3_pos_major_rows(int64_t B, int H, int W, int Cin, int Ho, int Wo, int64_t Cout, int64_t tiles_n64);
+int conv3x3_pos_major_raster();            // 1: the debug switch that keeps those tiles in raster order (Conv3x3Geom::raster) instead of longest first
 
 // Streaming variant for the HBM-bound Cin = 64 layers (stream1x1.hip): persistent workgroups, weights in registers, pixel tiles by LDS-DMA.
 bool conv1x1_stream_applicable(int64_t M, int Cin, int Cout, const float* x, const float* res);
