@@ -35,6 +35,13 @@
  *     (kh, kw, ci) in chunks of ISX_CONV_CHUNK terms -- that chain inside a chunk, the chunk
  *     sums added in order into a second fp32 accumulator (tot = tot + chain_c), then the
  *     epilogue on tot.  The 7x7 stem cuts after filter rows 2 and 5 (63 + 63 + 21 terms).
+ *   - special values (trunk and suffix-backward kernels): the sums above hold for NaN, infinities and subnormals too.  ReLU and the
+ *     max-pools are fmaxf: a NaN becomes 0 / loses to a number (torch propagates it).  Padding taps and k tails contribute
+ *     fma(0, w, acc) or fma(0, 0, acc): a non-finite ACTIVATION reaches exactly the outputs whose window holds it (the stem excepted: its
+ *     input must be finite, see isx_stem7x7_pool_nhwc); a non-finite WEIGHT under a padding tap gives NaN, except in the position-major
+ *     3x3 order, which skips padding taps (isx_conv3x3_expand128_nhwc below).  Subnormals are never flushed.  An overflowing chain
+ *     overflows at the term where the oracle's does.  The input-gradient kernels return +0 for a chain that ends on -0 (their epilogue adds an
+ *     absent bias as +0), and a weight-gradient split whose pixel count is no multiple of 32 does too (zero-filled k-tile slots).
  *   - operands may exceed 2^31 elements and 4 GiB except where an entry states a limit (and refuses, ISX_ERR_ARG, before any launch);
  *     tests/test_gpu_large_tensors.py holds this for every function below whose last parameter is `isx_stream_t stream`
  */
@@ -186,6 +193,11 @@ int isx_conv3x3_expand128_nhwc(const float* x, int64_t B, int H, int W, int Cin,
  * MaxPool2d(3, stride 2, padding 1) on a channels-last image batch; the convolution output never reaches memory.  Replaces
  * conv1, bn1, relu, maxpool of the torchvision ResNet `features` trunk (model/ModelDefinition.py, split by model/nn_utils.py:56-71,
  * run from model/siamese.py:20,107,151).  conv = fp32 fma chain over (kh, kw, c) ascending (bit-exact vs the oracle).
+ * x MUST BE FINITE (subnormals included; they are kept).  The kernel pads the 21 terms of a filter row to 22 with a zero weight, and the activation
+ * of that slot is real data: channel 0 of input column 2 wo + 4 of the same input row.  fma(x, 0, acc) = acc for a finite x only: a NaN or infinity
+ * in channel 0 of an EVEN column c >= 4 of input row hi makes, besides the outputs whose 7x7 window holds it, convolution column (c - 4) / 2 of the rows
+ * ho with |2 ho - hi| <= 3 NaN in every channel, which the ReLU turns into 0 before the pool.  Channels 1 and 2, odd columns and columns 0 and 2 reach
+ * their own window only.  tests/test_gpu_special_values.py pins exactly this.
  * x: (B,H,W,3) fp32, 16-B aligned, W % 4 == 0, W <= 896 (images wider than 224 are walked in column bands of 224 inside the workgroup); w_ohwi: (64,7,7,3); bias: (64); out: (B,Hp,Wp,64) with
  * Hc = (H-1)/2 + 1, Hp = (Hc-1)/2 + 1 (same for W). */
 int isx_stem7x7_pool_nhwc(const float* x, int64_t B, int H, int W, const float* w_ohwi, const float* bias, float* out,

@@ -11,6 +11,8 @@
 //     buffers, a step ahead; rows keep a 4-pixel zero border, rows outside the image are zero-filled: padding needs no test;
 //   * K is ordered (kh, kw, c) with the 21 values of a filter row padded to 22 (zero weight): the A operand of k-step s of filter row
 //     kh is the LDS word at lane_base + kh * row + 2 s (+ 24 per column block): ONE base register, everything else immediate offsets;
+//     the 22nd word is real data -- channel 0 of input column 2 wo + 4 -- and the slot is fma(x, 0, acc): neutral for a FINITE x only, which
+//     is the input contract of isx_stem7x7_pool_nhwc (include/isx.h; a select that zeroes the operand cost 0.8 % of the kernel, docs/rounds/r19.md);
 //     the weights sit in LDS as [k][64] for the whole kernel (one ds_read per 7 MFMAs);
 //   * an accumulator row block is 4 columns x 8 rows, ordered so that ONE lane holds, for its channel, the 8 rows of two adjacent
 //     columns = four complete 2x2 pooling cells: the 3x3/2 max needs only the row above (carried in registers from the previous

@@ -161,6 +161,24 @@ def assert_bits(got, want, what=""):
     assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist(), got[bad][:4].tolist(), want[bad][:4].tolist())
 
 
+def assert_special(got, want, what="", fold_zero_sign=False):
+    """assert_bits for operands with NaN, infinities and subnormals (tests/test_gpu_special_values.py): the NaN positions are the same set, every
+    other element is equal bit for bit; the sign and payload of a NaN are free.  fold_zero_sign: -0 counts as +0 (max(-0, +0) of the bias and
+    pool kernels under ReLU only: the one sign IEEE leaves open)."""
+    from _special_values import compare
+    got = got.host() if isinstance(got, Region) else (got.cpu().numpy() if isinstance(got, torch.Tensor) else got)
+    compare(got, np.asarray(want), what, fold_zero_sign)
+
+
+def assert_same_special(a, b, what=""):
+    """Two device results of one call under assert_special's rule, compared on the device (large bodies)."""
+    a, b = (r.body if isinstance(r, Region) else r for r in (a, b))
+    na, nb = torch.isnan(a), torch.isnan(b)
+    assert torch.equal(na, nb), ("NaN positions differ between the two runs", what, int((na != nb).sum()))
+    bad = (a.contiguous().view(torch.int32) != b.contiguous().view(torch.int32)) & ~na
+    assert not bool(bad.any()), ("bits differ between the two runs", what, int(bad.sum()))
+
+
 # ---- host arithmetic of the launchers (csrc/gemm.hip, csrc/conv.hip), restated so that a case can assert the path it means to take ----------
 def tail_split_rows(M, N, slots=512):
     """gemm_tail_split_rows: rows covered by whole rounds of 128x128 tiles when the last round is partial (0: no split)."""
