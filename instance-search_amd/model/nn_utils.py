@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from isx import backbones as models
+from isx import ops
 
 
 def set_untrained_blocks(containers, n):
@@ -73,23 +74,6 @@ def extract_layers(net):
     return net.features, nn.Sequential(), net.classifier
 
 
-# A/B switches (environment).  ISX_CONV1X1=0 sends the 1x1 trunk convolutions back to MIOpen.  ISX_CONV3X3: "auto"
-# (default) runs the implicit-GEMM kernel where it wins on MI355X -- every 3x3 convolution of a BN-folded residual block (round 2,
-# with the buffer-instruction epilogue: 1.93-1.98 ms against MIOpen's igemm + zero fill + separate epilogue pass 2.05-2.15 ms at
-# Cin >= 256, B = 1024; ResNet-50 extraction +2-3 % at B = 256 and at 448x448) and stand-alone convolutions BEHIND A BATCHNORM with
-# Cin <= 128 -- "1" everywhere, "0" never, an integer N > 1: Cin <= N.  (The 13x13 AlexNet layers, 192->384, 384->256, 256->256, have no
-# BatchNorm: they are ISX_ALEX's, below, which re-measured the -5 % once noted here with the ReLU fused: +11 %.)
-_CONV3X3_MODE = os.environ.get("ISX_CONV3X3", "auto")
-_IMPLICIT_GEMM_3X3 = _CONV3X3_MODE != "0"
-_GEMM_1X1 = os.environ.get("ISX_CONV1X1", "1") != "0"
-_FUSE_EXPAND = os.environ.get("ISX_FUSE_EXPAND", "1") != "0"     # 0: conv2 and conv3 of the 64- and 128-channel identity bottlenecks as two kernels again
-_FUSED_STEM = os.environ.get("ISX_STEM", "1") != "0"       # 0: stem convolution back to MIOpen + the separate bias/ReLU/maxpool pass
-_FUSE_PROJECTION = os.environ.get("ISX_FUSE_PROJECTION", "1") != "0"     # last 1x1 conv + projection shortcut as one GEMM
-if not (_GEMM_1X1 and _FUSED_STEM and _FUSE_EXPAND and _FUSE_PROJECTION and _CONV3X3_MODE == "auto"):
-    import warnings
-    warnings.warn("libisx A/B switches are set (ISX_CONV1X1 / ISX_CONV3X3 / ISX_STEM / ISX_FUSE_EXPAND / ISX_FUSE_PROJECTION): some trunk "
-                  "convolutions run on MIOpen or unfused in this process -- a measurement aid, not the product path")
-
 # ISX_ALEX: the convolutions without a BatchNorm behind them and the MaxPool2d(3, 2) of an AlexNet-style `features` (isx.backbones.alexnet,
 # model.ModelDefinition.Maxnet).  "1": every one of them runs on libisxalex (isx/alex.py: general K x K convolution with the trunk's canonical sum,
 # un-padded 3 / 2 max-pool) or, the 3x3 / padding 1 layers with Cin % 32 == 0, on libisx's isx_conv3x3_nhwc -- no torch convolution or pool on
@@ -136,59 +120,71 @@ def invalidate_derived_weights(module):
                 m.__dict__[slot] = None
 
 
-class _ConvBiasAct(nn.Module):
-    """Bias-free convolution + fused `y = act(y + bias (+ residual))` epilogue (libisx `isx_bias_act_inplace` on
-    the GPU, plain torch otherwise)."""
+def _native(x):
+    """The ONE per-input test of the folded ResNet trunk: what the libisx convolution kernels take -- an fp32 GPU tensor without an autograd
+    graph whose memory is channels-last.  A tensor that is dense in both formats (H = W = 1, or C = 1) counts as NCHW: the torch route."""
+    return x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and ops._is_nhwc(x)
 
-    def __init__(self, conv, relu):
+
+def _as_nhwc(t):
+    if t is None or t.is_contiguous(memory_format=torch.channels_last):
+        return t
+    return t.contiguous(memory_format=torch.channels_last)
+
+
+def _is_3x3(c, strides, cin_multiple):
+    return (c.kernel_size == (3, 3) and c.padding == (1, 1) and c.groups == 1 and c.dilation == (1, 1) and c.stride in strides
+            and c.in_channels % cin_multiple == 0)
+
+
+def _is_1x1(c, strides):
+    return c.kernel_size == (1, 1) and c.padding == (0, 0) and c.groups == 1 and c.stride in strides
+
+
+class _ConvBiasAct(nn.Module):
+    """Bias-free convolution + fused `y = act(y + bias (+ residual))` epilogue.  `kind`, fixed here from the convolution's geometry, names
+    what runs it on a `_native` input: "conv3x3" (isx_conv3x3_nhwc: implicit GEMM on the fp32 matrix cores), "conv1x1" (isx_conv1x1_nhwc: one
+    fp32-MFMA GEMM over the pixels), both with the epilogue fused, or "torch" (torch's convolution, then libisx `isx_bias_act_inplace` on the
+    GPU, plain torch otherwise) -- which is also what every other input gets.  `in_block`: a convolution of a BN-folded residual block
+    (_FusedBlock).  The 3x3 kernel takes every one of those (1.93-1.98 ms against MIOpen's igemm + zero fill + separate epilogue pass
+    2.05-2.15 ms at Cin >= 256, B = 1024; ResNet-50 extraction +2-3 % at B = 256 and at 448x448), a stand-alone layer behind a BatchNorm
+    only up to Cin = 128.  (Layers without a BatchNorm, the AlexNet ones, are ISX_ALEX's, above.)
+    `plain`: no epilogue of its own on the torch route and a zero bias (projection shortcut: its bias is merged into the block's last)."""
+
+    def __init__(self, conv, relu, in_block=False, plain=False):
         super().__init__()
         bias = conv.bias.detach().clone() if conv.bias is not None else torch.zeros(conv.out_channels)
         self.conv = nn.Conv2d(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding, conv.dilation,
                               conv.groups, bias=False)
         self.conv.weight = nn.Parameter(conv.weight.detach().clone(), requires_grad=False)
-        self.bias = nn.Parameter(bias, requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros_like(bias) if plain else bias, requires_grad=False)
         self.relu = relu
-        self.plain = False            # True: no epilogue of its own (projection shortcut, bias merged elsewhere)
-        self.in_block = False         # True: a convolution of a BN-folded residual block (_FusedBlock)
+        self.in_block = in_block
+        self.plain = plain
+        c = self.conv
+        if _is_3x3(c, ((1, 1), (2, 2)), 32) and (in_block or c.in_channels <= 128):
+            self.kind = "conv3x3"
+        elif _is_1x1(c, ((1, 1),)) and c.dilation == (1, 1):
+            self.kind = "conv1x1"
+        else:
+            self.kind = "torch"
 
     def w_ohwi(self):
         """(Cout,kh,kw,Cin) copy of the weight for the implicit-GEMM / stem kernels; follows the weight (see _derived)."""
         w = self.conv.weight
         return _derived(self, '_c_w_ohwi', (w,), lambda: w.detach().permute(0, 2, 3, 1).contiguous())
 
-    def _pointwise(self):
-        c = self.conv
-        return _GEMM_1X1 and c.kernel_size == (1, 1) and c.padding == (0, 0) and c.groups == 1 and c.dilation == (1, 1) and c.stride == (1, 1)
-
-    def _three_by_three(self):
-        c = self.conv
-        return (_IMPLICIT_GEMM_3X3 and c.kernel_size == (3, 3) and c.padding == (1, 1) and c.groups == 1 and c.dilation == (1, 1)
-                and c.stride in ((1, 1), (2, 2)) and c.in_channels % 32 == 0
-                and (_CONV3X3_MODE == "1" or (_CONV3X3_MODE == "auto" and self.in_block)
-                     or c.in_channels <= (int(_CONV3X3_MODE) if _CONV3X3_MODE.isdigit() and int(_CONV3X3_MODE) > 1 else 128)))
-
     def forward(self, x, residual=None):
-        if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and self._three_by_three()
-                and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
-            # 3x3 convolution on channels-last activations: implicit GEMM on the fp32 matrix cores, epilogue fused
-            from isx import ops
-            if residual is not None and not residual.is_contiguous(memory_format=torch.channels_last):
-                residual = residual.contiguous(memory_format=torch.channels_last)
-            return ops.conv3x3_nhwc(x, self.w_ohwi(), self.bias, self.conv.stride[0], residual, self.relu)
-        if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and self._pointwise()
-                and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
-            # 1x1 convolution on channels-last activations: one fp32-MFMA GEMM over the pixels, epilogue fused
-            from isx import ops
-            if residual is not None and not residual.is_contiguous(memory_format=torch.channels_last):
-                residual = residual.contiguous(memory_format=torch.channels_last)
-            return ops.conv1x1_nhwc(x, self.conv.weight, self.bias, residual, self.relu)
+        if self.kind != "torch" and _native(x):
+            if self.kind == "conv3x3":
+                return ops.conv3x3_nhwc(x, self.w_ohwi(), self.bias, self.conv.stride[0], _as_nhwc(residual), self.relu)
+            return ops.conv1x1_nhwc(x, self.conv.weight, self.bias, _as_nhwc(residual), self.relu)
         y = self.conv(x)
         if y.is_cuda:
             _note_torch_conv(self.conv)
         if self.plain:
             return y
         if y.is_cuda and y.dtype == torch.float32 and not torch.is_grad_enabled():
-            from isx import ops
             if residual is not None and residual.stride() != y.stride():
                 residual = residual.contiguous(memory_format=torch.channels_last if not y.is_contiguous() else torch.contiguous_format)
             return ops.bias_act_(y, self.bias, residual, self.relu)
@@ -217,21 +213,15 @@ class _StemConvPool(nn.Module):
     def forward(self, x):
         c = self.cba
         if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and c.conv.out_channels % 4 == 0):
-            from isx import ops
-            if _FUSED_STEM and ops.stem7x7_pool_applicable(x, c.conv):
+            if ops.stem7x7_pool_applicable(x, c.conv):
                 # images up to 896 wide: convolution + bias + ReLU + pooling as ONE kernel, nothing in between touches memory
                 return ops.stem7x7_pool(x, c.w_ohwi(), c.bias)
             y = c.conv(x)
             _note_torch_conv(c.conv)
             if y.is_contiguous(memory_format=torch.channels_last) and not y.is_contiguous():
                 return ops.bias_relu_maxpool(y, c.bias)
-            return self.pool(ops_bias_act(y, c.bias, c.relu))
+            return self.pool(ops.bias_act_(y, c.bias, None, c.relu))
         return self.pool(c(x))
-
-
-def ops_bias_act(y, bias, relu):
-    from isx import ops
-    return ops.bias_act_(y, bias, None, relu)
 
 
 def _is_stem_pool(m):
@@ -242,20 +232,47 @@ def _is_stem_pool(m):
 class _FusedBlock(nn.Module):
     """Inference form of a (BN-folded) BasicBlock / Bottleneck: relu(convN(...) + bias + identity) with every
     bias / residual / ReLU fused into one in-place pass per convolution.  The projection shortcut keeps no
-    epilogue of its own: its bias is added to the last convolution's bias."""
+    epilogue of its own: its bias is added to the last convolution's bias.
+
+    `route`, fixed here from the folded convolutions, names the fused kernel that runs the block's tail on a `_native` input:
+      "dual"         relu(conv_last(t) + projection(x) + bias) as ONE GEMM over [t ; x_strided] (isx_conv1x1_dual_nhwc): the shortcut tensor
+                     is never materialised
+      "expand_dual"  first block of the 64-channel stage: conv2 + conv3 + projection + ReLU as ONE kernel (isx_conv3x3_expand_dual_nhwc)
+      "expand64"     identity Bottleneck with 64 mid channels (ResNet stage 1): conv2 + conv3 + residual + ReLU as ONE kernel
+                     (isx_conv3x3_expand_nhwc): the mid activation never reaches memory
+      "expand128"    identity Bottleneck with 128 mid channels (ResNet stage 2, blocks 1..): the same as ONE kernel
+                     (isx_conv3x3_expand128_nhwc): the 128 x 128 accumulator tile of conv2 IS the A operand of conv3
+      None           no fused tail: one call per convolution, which is also what every other input gets."""
 
     def __init__(self, convs, downsample):
         super().__init__()
-        self.convs = nn.ModuleList([_ConvBiasAct(c, relu=True) for c in convs])
-        for c in self.convs:
-            c.in_block = True
+        self.convs = nn.ModuleList([_ConvBiasAct(c, relu=True, in_block=True) for c in convs])
         self.downsample = None
         if downsample is not None:
-            d = _ConvBiasAct(downsample, relu=False)
-            d.bias = nn.Parameter(torch.zeros_like(d.bias), requires_grad=False)
-            d.plain = True
-            self.convs[-1].bias = nn.Parameter(self.convs[-1].bias + _ConvBiasAct(downsample, relu=False).bias, requires_grad=False)
-            self.downsample = d                                             # projection (its bias lives in the last conv's epilogue)
+            last = self.convs[-1]
+            d_bias = downsample.bias.detach() if downsample.bias is not None else torch.zeros(downsample.out_channels)
+            last.bias = nn.Parameter(last.bias + d_bias, requires_grad=False)
+            self.downsample = _ConvBiasAct(downsample, relu=False, plain=True)      # projection (its bias lives in the last conv's epilogue)
+        self.route = self._route()
+
+    def _route(self):
+        last, d = self.convs[-1], self.downsample
+        c2 = self.convs[1].conv if len(self.convs) == 3 else None
+        # conv2 of a Bottleneck as the fused expansion kernels take it: 3x3 / stride 1 with a ReLU behind it, conv3 a plain 1x1 GEMM
+        mid = c2.out_channels if (c2 is not None and _is_3x3(c2, ((1, 1),), 32) and self.convs[1].relu and last.kind == "conv1x1"
+                                  and last.conv.in_channels == c2.out_channels) else None
+        if d is not None:
+            if not (last.kind == "conv1x1" and _is_1x1(d.conv, ((1, 1), (2, 2))) and last.conv.in_channels % 32 == 0 and d.conv.in_channels % 32 == 0):
+                return None
+            if mid == 64 and last.conv.out_channels == 256 and d.conv.in_channels == 64 and d.conv.stride == (1, 1):
+                return "expand_dual"
+            return "dual"
+        block_in, cout = self.convs[0].conv.in_channels, last.conv.out_channels
+        if mid == 64 and cout == 256 and block_in == 256:
+            return "expand64"
+        if mid == 128 and c2.in_channels % 64 == 0 and cout % 128 == 0 and block_in == cout:
+            return "expand128"
+        return None
 
     def w_cat(self):
         """[W_last | W_projection] (Cout, K1 + K2) for the fused last-conv + shortcut GEMM; follows both weights (see _derived)."""
@@ -271,78 +288,22 @@ class _FusedBlock(nn.Module):
             return _derived(self, '_c_w3t', (wl, wd), lambda: self.w_cat().t().contiguous())
         return _derived(self, '_c_w3t', (wl,), lambda: wl.detach().reshape(wl.shape[0], -1).t().contiguous())
 
-    def _fusable_projection(self, x):
-        last, d = self.convs[-1], self.downsample
-        return (_GEMM_1X1 and _FUSE_PROJECTION and d is not None and last._pointwise() and d.conv.kernel_size == (1, 1) and d.conv.padding == (0, 0)
-                and d.conv.groups == 1 and d.conv.stride in ((1, 1), (2, 2)) and last.conv.in_channels % 32 == 0 and d.conv.in_channels % 32 == 0
-                and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
-
-    def _fusable_expand_dual(self):
-        if not (_FUSE_EXPAND and _IMPLICIT_GEMM_3X3 and len(self.convs) == 3):
-            return False
-        c2, c3, d = self.convs[1].conv, self.convs[2].conv, self.downsample.conv
-        return (c2.kernel_size == (3, 3) and c2.padding == (1, 1) and c2.groups == 1 and c2.dilation == (1, 1) and c2.stride == (1, 1)
-                and c2.out_channels == 64 and c2.in_channels % 32 == 0 and self.convs[1].relu and c3.in_channels == 64 and c3.out_channels == 256
-                and d.in_channels == 64 and d.stride == (1, 1))
-
-    def _fusable_expand(self, x):
-        if not (_FUSE_EXPAND and _GEMM_1X1 and _IMPLICIT_GEMM_3X3 and self.downsample is None and len(self.convs) == 3):
-            return False
-        c2, c3 = self.convs[1].conv, self.convs[2].conv
-        return (c2.kernel_size == (3, 3) and c2.padding == (1, 1) and c2.groups == 1 and c2.dilation == (1, 1) and c2.stride in ((1, 1), (2, 2))
-                and c2.out_channels == 64 and c2.in_channels % 32 == 0 and self.convs[1].relu and self.convs[2]._pointwise() and c3.in_channels == 64
-                and c3.out_channels == 256 and x.shape[1] == 256 and c2.stride == (1, 1)
-                and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
-
-    def _fusable_expand128(self, x):
-        if not (_FUSE_EXPAND and _GEMM_1X1 and _IMPLICIT_GEMM_3X3 and self.downsample is None and len(self.convs) == 3):
-            return False
-        c2, c3 = self.convs[1].conv, self.convs[2].conv
-        return (c2.kernel_size == (3, 3) and c2.padding == (1, 1) and c2.groups == 1 and c2.dilation == (1, 1) and c2.stride == (1, 1)
-                and c2.out_channels == 128 and c2.in_channels % 64 == 0 and self.convs[1].relu and self.convs[2]._pointwise() and c3.in_channels == 128
-                and c3.out_channels % 128 == 0 and x.shape[1] == c3.out_channels
-                and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
-
     def forward(self, x):
-        if self._fusable_projection(x):
-            # relu(conv_last(t) + projection(x) + bias) as ONE GEMM over [t ; x_strided] (libisx isx_conv1x1_dual_nhwc):
-            # the shortcut tensor is never materialised
-            from isx import ops
-            last, d = self.convs[-1], self.downsample
-            if self._fusable_expand_dual():
-                # first block of the 64-channel stage: conv2 + conv3 + projection + ReLU as ONE kernel (isx_conv3x3_expand_dual_nhwc)
-                c2 = self.convs[1]
-                t = self.convs[0](x)
-                if not t.is_contiguous(memory_format=torch.channels_last):
-                    t = t.contiguous(memory_format=torch.channels_last)
+        if self.route is not None and _native(x):
+            last = self.convs[-1]
+            if self.route == "dual":
+                t = x
+                for c in self.convs[:-1]:
+                    t = c(t)
+                return ops.conv1x1_dual_nhwc(_as_nhwc(t), x, self.w_cat(), last.bias, self.downsample.conv.stride[0], last.relu)
+            c2 = self.convs[1]
+            t = _as_nhwc(self.convs[0](x))
+            if self.route == "expand_dual":
                 return ops.conv3x3_expand_dual_nhwc(t, c2.w_ohwi(), c2.bias, x, self.w3t(), last.bias, last.relu)
-            t = x
-            for c in self.convs[:-1]:
-                t = c(t)
-            if not t.is_contiguous(memory_format=torch.channels_last):
-                t = t.contiguous(memory_format=torch.channels_last)
-            return ops.conv1x1_dual_nhwc(t, x, self.w_cat(), last.bias, d.conv.stride[0], last.relu)
-        if self._fusable_expand(x):
-            # Bottleneck with 64 mid channels and an identity shortcut (ResNet stage 1): conv2 + conv3 + residual + ReLU as ONE kernel
-            # (libisx isx_conv3x3_expand_nhwc): the mid activation never reaches memory
-            from isx import ops
-            c2, c3 = self.convs[1], self.convs[2]
-            t = self.convs[0](x)
-            if not t.is_contiguous(memory_format=torch.channels_last):
-                t = t.contiguous(memory_format=torch.channels_last)
-            return ops.conv3x3_expand_nhwc(t, c2.w_ohwi(), c2.bias, c2.conv.stride[0], self.w3t(), c3.bias, x, c3.relu)
-        if self._fusable_expand128(x):
-            # Bottleneck with 128 mid channels and an identity shortcut (ResNet stage 2, blocks 1..): conv2 + conv3 + residual + ReLU as ONE
-            # kernel (libisx isx_conv3x3_expand128_nhwc): the 128 x 128 accumulator tile of conv2 IS the A operand of conv3
-            from isx import ops
-            c2, c3 = self.convs[1], self.convs[2]
-            t = self.convs[0](x)
-            if not t.is_contiguous(memory_format=torch.channels_last):
-                t = t.contiguous(memory_format=torch.channels_last)
-            return ops.conv3x3_expand128_nhwc(t, c2.w_ohwi(), c2.bias, self.w3t(), c3.bias, x, c3.relu)
+            if self.route == "expand64":
+                return ops.conv3x3_expand_nhwc(t, c2.w_ohwi(), c2.bias, c2.conv.stride[0], self.w3t(), last.bias, x, last.relu)
+            assert self.route == "expand128", self.route
+            return ops.conv3x3_expand128_nhwc(t, c2.w_ohwi(), c2.bias, self.w3t(), last.bias, x, last.relu)
         idt = x if self.downsample is None else self.downsample(x)
         y = x
         for c in self.convs[:-1]:
@@ -355,6 +316,8 @@ def _alex_native(kind):
 
 
 def _gpu_inference_nhwc(x):
+    # not _native: a map that is dense in both memory formats (H = W = 1, or C = 1) counts as channels-last HERE and goes to the AlexNet
+    # kernels; making the two one would change which library computes such a map
     return (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last))
 
@@ -386,7 +349,6 @@ class _AlexConv(nn.Module):
         if _alex_native(self.kind) and _gpu_inference_nhwc(x):
             bias = c.bias if c.bias is not None else self.no_bias
             if self.libisx_3x3:
-                from isx import ops
                 return ops.conv3x3_nhwc(x, self.w_ohwi(), bias, c.stride[0], None, self.act is not None)
             from isx import alex
             if x.data_ptr() % 16:
