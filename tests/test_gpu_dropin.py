@@ -590,6 +590,38 @@ def test_folded_trunk_follows_load_state_dict():
             p.data.copy_(q.data)
         invalidate_derived_weights(fa)
         assert torch.equal(fa(x), folded(2)(x))
+    # single blocks with non-trivial biases against the model (tests/_trunk_model.py): the re-laid-out copies ([W3 | Wd], its transpose, OHWI)
+    # follow the weights through a device move, through load_state_dict(assign=True) and through copy.deepcopy of a block whose caches are filled
+    import copy
+    import _guards as G
+    import _trunk_model as TM
+    for cid in ("expand_dual", "dual_s2"):
+        xn = TM.case_inputs(cid)[0][0]
+        xg = torch.from_numpy(xn).cuda().permute(0, 3, 1, 2)
+
+        def follows(blk, what):
+            with torch.no_grad():
+                got = blk(xg)
+            G.assert_bits(got.permute(0, 2, 3, 1).contiguous().cpu().numpy(), TM.block_reference(blk, xn), "%s: %s" % (cid, what))
+            return got
+        blk = TM.fold(TM.make_block(cid))
+        with torch.no_grad():
+            blk(torch.from_numpy(xn).permute(0, 3, 1, 2))                          # a first forward on the CPU ...
+            cpu_copies = [blk.w_cat(), blk.w3t(), blk.convs[1].w_ohwi()]           # ... and every derived copy built there
+        assert all(not t.is_cuda for t in cpu_copies)
+        blk = blk.cuda().to(memory_format=torch.channels_last)
+        y_first = follows(blk, "CPU forward, then .cuda()")
+        other = TM.fold(TM.randomise_bn(TM.make_block(cid), 77)).cuda()
+        blk.load_state_dict(other.state_dict(), assign=True)
+        y_other = follows(blk, "load_state_dict(assign=True)")
+        assert not torch.equal(y_other, y_first)
+        twin = copy.deepcopy(blk)                                                  # the caches are filled: they are copied along
+        with torch.no_grad():
+            for w in (twin.convs[1].conv.weight, twin.convs[-1].conv.weight, twin.downsample.conv.weight):
+                w.mul_(2)
+        y_twin = follows(twin, "deepcopy, then weight.mul_(2) on the copy")
+        assert not torch.equal(y_twin, y_other)
+        assert torch.equal(follows(blk, "the original behind its copy's mul_"), y_other)
 
 
 def test_streaming_ingest_matches_resident_path(monkeypatch):
