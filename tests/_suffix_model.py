@@ -60,6 +60,41 @@ def split_ranges(K, S):
     return kt_per, [(min(K, BK * s * kt_per), min(K, BK * (s + 1) * kt_per)) for s in range(S)]
 
 
+# ---- the tile shape of isx_conv3x3_dgrad_nhwc ---------------------------------------------------------------------------------------------
+# A restatement of pick_tile_cfg (csrc/gemm.hip) as host arithmetic.  The library does not export that function and the gradient entry has no tile
+# hook, so NOTHING can check this restatement against the library: it is the source read into Python, in IEEE doubles as the C++ is (the
+# efficiencies are floats there and widened to double in the division, as float(np.float32(.)) is here).
+TILE_CFGS = ((2, 2, 4), (1, 2, 4), (2, 1, 4), (1, 1, 6))              # (tm, tn, resident workgroups per CU) of 128x128, 64x128, 128x64, 64x64
+TILE_TAIL = (0.22, 0.25, 0.25, 0.15)
+EFF_3X3 = tuple(float(np.float32(e)) for e in (0.90, 0.0, 0.865, 0.87))    # kEff3x3 of csrc/conv.hip
+MASK_3X3 = 0xD                                                        # the convolutions have no 64x128 instance
+
+
+def tile_times(M, N, eff=EFF_3X3, mask=MASK_3X3, wg_per_cu_128=4):
+    """(4, ...) estimated times of the four tile shapes for M rows (an int or an int64 array) and N columns, split = 0; inf outside `mask`."""
+    M = np.asarray(M, dtype=np.int64)
+    out = np.full((4,) + M.shape, np.inf)
+    for c, (tm, tn, wg) in enumerate(TILE_CFGS):
+        if not (mask >> c) & 1:
+            continue
+        if c == 0:
+            wg = wg_per_cu_128
+        tiles = ((M + 64 * tm - 1) // (64 * tm)).astype(np.float64) * float((N + 64 * tn - 1) // (64 * tn))
+        x = tiles / (256.0 * wg)
+        t0 = TILE_TAIL[c]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rounds = x + np.where(x <= 0.7, t0, t0 * (0.7 / x) * (0.7 / x))
+        per_cu = np.floor((tiles + 255.0) / 256.0) / wg
+        rounds = np.where(rounds > per_cu, rounds, per_cu)
+        out[c] = rounds * wg * (tm * tn) / eff[c]
+    return out
+
+
+def pick_tile_cfg(M, N, eff=EFF_3X3, mask=MASK_3X3, wg_per_cu_128=4):
+    """Index into TILE_CFGS of the shape with the smallest estimated time; the first wins a tie (the C++ compares with <)."""
+    return np.argmin(tile_times(M, N, eff, mask, wg_per_cu_128), axis=0)
+
+
 def colsum(rows):
     """s = 0; s += row, in row order."""
     s = np.zeros(rows.shape[1], F)

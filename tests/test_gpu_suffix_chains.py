@@ -197,8 +197,13 @@ def test_dgrad1x1_is_one_chain_then_add_then_mask(Cout, Cin, M):
 def test_dgrad3x3_is_one_chain_over_the_neighbourhood(name):
     """One chain of 9 * Cout terms in (kh, kw, co) order over the zero-padded neighbourhood, then the mask; with and without mask (a call without
     mask used to take the inference kernel's two-level sum: the gradient instance is now chosen by the entry, not by the mask).  This entry has no
-    tile hook: by pick_tile_cfg every case here (up to 144 pixels x 96 channels, a fraction of one round of the chip) takes the 64x64 tile; the
-    128x64 and 128x128 instances of the GRAD path run only at the sizes of the whole-step tests (tests/test_gpu_suffix.py, 1e-5 against float64)."""
+    tile hook: by pick_tile_cfg (restated in _suffix_model.py; tests/test_suffix_engine_model.py asserts what follows on the CPU) every case here
+    (up to 144 pixels x 96 channels, a fraction of one round of the chip) takes the 64x64 tile -- and so do layer4's launches in the whole-step
+    tests (tests/test_gpu_suffix.py: 1176 x 512 for one leaf, 9408 x 512 for eight).  The 128x128 instance of the GRAD path is chosen from
+    38 913 pixels x 512 channels on (77 825 x 256, 155 649 x 128).  Two tests run it, both against dgrad3x3 of this model: the case of
+    tests/test_gpu_large_tensors.py (171 199 images of 7 x 7 = 8 388 751 pixels x 256 channels, its period rows compared) and the one of
+    tests/test_gpu_suffix_engine.py at the first such row count (38 913 x 512: the last tile has one live row).  The 128x64 instance is never
+    chosen for 64 .. 2048 channels and up to 3 000 000 pixels: under the automatic choice no test can reach it."""
     L, check, st = _lib()
     B, H, W, Cout, Cin, _ = model.DGRAD3_CASES[name]
     dz_np, wt_np, mask_np, v = model.dgrad3_case(name)
